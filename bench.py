@@ -17,10 +17,18 @@ Parallel layout (the metric is "... at 1/2/4/8-stage pipeline"):
     GPU, the layer split chosen by the planner's hop/compute model, 1F1B micro-batching, and
     the native multi-rank step (parallel/native_step.py: one C++ call per step, RCCL P2P on
     per-direction communicators, DP buckets on their own stream);
-  * after the pipeline number, the same N GPUs also run pure data parallelism (``dp_only`` in
-    the JSON; ``--no-dp-compare`` skips it);
+  * ``--full``: after the pipeline number, the same N GPUs also run pure data parallelism
+    (``dp_only`` in the JSON; ``--no-dp-compare`` skips it) and, after a replicated-stage
+    layout, the literal uniform grid (``uniform_pipeline``). A plain run measures the headline
+    layout only;
   * ``ppS`` / ``dpN`` / ``ppSdpD`` force a layout; ``best`` lets the planner pick.
 Weak scaling: every GPU contributes ``--batch`` rows per step.
+
+``--dump-outputs DIR``: after the timed steps, what the last of them left a caller with -- the
+fp32 master weights and biases of every layer (``w<k>.npy``, ``b<k>.npy``) and the mean loss
+(``loss.npy``, float64) -- is written to DIR. Weights, data and batch order are seeded, so two
+runs with the same arguments start from identical inputs. Across ranks every rank writes the
+layers it holds as ``w<k>.rank<r>.npy`` and rank 0 writes the loss.
 """
 from __future__ import annotations
 
@@ -101,6 +109,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-dp-compare", action="store_true",
                     help="N > 1: skip the data-parallel-only comparison run")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="N > 1: after the headline number also measure the comparison layouts "
+                         "(data parallelism only; the uniform grid after a replicated-stage "
+                         "layout). Off by default: a plain run times the headline layout only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results (per-layer fp32 weights and "
+                         "biases, the loss) to DIR as .npy files")
     return ap.parse_args(argv)
 
 
@@ -178,8 +193,24 @@ def first_step_guard(tr, one_step, dev, timeout_s):
     th.join()
 
 
-def measure(a, spec, n, world, dev, text):
-    """Build the trainer for one layout, W warm-up + K timed steps; returns the JSON fields."""
+def dump_outputs(d, tr, loss, world):
+    """--dump-outputs: the state the last timed step produced, as DIR/<name>.npy (a few MB for
+    the named models). Every rank calls this (sharded optimizers gather their pieces)."""
+    import numpy as np
+
+    rank = int(os.environ.get("RANK", "0"))
+    sfx = f".rank{rank}" if world > 1 else ""
+    os.makedirs(d, exist_ok=True)
+    for k, (w, b) in tr.local_weights().items():
+        np.save(os.path.join(d, f"w{k}{sfx}.npy"), np.asarray(w, dtype=np.float32))
+        np.save(os.path.join(d, f"b{k}{sfx}.npy"), np.asarray(b, dtype=np.float32))
+    if rank == 0 and loss is not None:
+        np.save(os.path.join(d, "loss.npy"), np.asarray([loss], dtype=np.float64))
+
+
+def measure(a, spec, n, world, dev, text, dump=""):
+    """Build the trainer for one layout, W warm-up + K timed steps; returns the JSON fields.
+    ``dump``: directory for the last timed step's outputs (dump_outputs)."""
     plan = _plan(a, spec, n, world, text)
     fan = plan.reps is not None and (len(set(plan.reps)) > 1 or plan.colocated)
     lay = FanLayout(tuple(plan.distribution), tuple(plan.reps), plan.place) if fan else None
@@ -331,6 +362,8 @@ def measure(a, spec, n, world, dev, text):
         lt = torch.tensor([loss if loss is not None else -1.0], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(lt, op=torch.distributed.ReduceOp.MAX)
         loss = float(lt.item())
+    if dump:
+        dump_outputs(dump, tr, loss, world)
     value = global_batch * a.steps / elapsed
     out = {
         "value": round(value, 1), "ms_per_step": round(elapsed / a.steps * 1e3, 4),
@@ -410,9 +443,9 @@ def supervise(a, argv) -> int:
     climbing the fallback ladder until one attempt succeeds on every rank. Then, while the time
     left allows, two comparisons run the same way: the literal uniform ppS x dpD pipeline of
     BASELINE.json (when the main layout was a replicated-stage "fan" pipeline) and pure data
-    parallelism. Rank 0 prints the one JSON line, with every attempt (rung, exit codes, last
-    heartbeat of a stalled child) listed -- also when the job is ended by SIGTERM
-    (ladder.OneLine), so a bench the driver stops at its deadline still reports.
+    parallelism (both with ``--full`` only). Rank 0 prints the one JSON line, with every attempt
+    (rung, exit codes, last heartbeat of a stalled child) listed -- also when the job is ended
+    by SIGTERM (ladder.OneLine), so a bench the driver stops at its deadline still reports.
 
     Time: a failing rung costs at most a child's start-up + the first-step guard
     (DNN_FIRST_STEP_TIMEOUT, 30 s) or a heartbeat stall (DNN_LADDER_STALL, 60 s); past
@@ -468,8 +501,12 @@ def supervise(a, argv) -> int:
 
     line = ladder.OneLine(rank, build)
     line.install_sigterm()  # before the Supervisor's handler, which chains to it
-    sup = ladder.Supervisor(lambda r: [*base, *r.args, "--no-dp-compare"], rank=rank,
-                            world=world, stall=float(switches.get("DNN_LADDER_STALL")),
+    # a comparison's children must not overwrite what the headline attempt dumped (the later
+    # --dump-outputs wins; st["pending"] is set once the comparisons start)
+    sup = ladder.Supervisor(lambda r: [*base, *r.args, "--no-dp-compare",
+                                       *(["--dump-outputs", ""] if st.get("pending") else [])],
+                            rank=rank, world=world,
+                            stall=float(switches.get("DNN_LADDER_STALL")),
                             startup=float(switches.get("DNN_LADDER_STARTUP")),
                             deadline=t_start + float(switches.get("DNN_LADDER_DEADLINE")))
     is_fan = False
@@ -489,9 +526,9 @@ def supervise(a, argv) -> int:
         lay = res["config"]["parallelism"]
         items = []
         # the literal BASELINE grid, measured, when the main number came from a fan layout
-        if is_fan and lay.startswith("fan"):
+        if a.full and is_fan and lay.startswith("fan"):
             items.append(("uniform_pipeline", ladder.uniform_rungs()))
-        if not a.no_dp_compare and not lay.startswith(("dp", "tp")):
+        if a.full and not a.no_dp_compare and not lay.startswith(("dp", "tp")):
             items.append(("dp_only", ladder.bench_rungs(world, dp_only=True)))
         st["pending"] = [k for k, _ in items]
         need = 1.5 * sup.attempts[-1]["seconds"] + 30
@@ -523,18 +560,21 @@ def main(argv=None):
         ladder.heartbeat("rendezvous done")
 
     if a.parallelism.startswith("tp"):
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: not available for tensor-parallel layouts")
         m = measure_tp(a, spec, n, world, dev)
     else:
-        m = measure(a, spec, n, world, dev, a.parallelism)
+        m = measure(a, spec, n, world, dev, a.parallelism, dump=a.dump_outputs)
     uniform = _uniform_prediction(a, spec, n, world)
-    if world > 1 and not ladder.is_child() and m["parallelism"].startswith("fan"):
+    if a.full and world > 1 and not ladder.is_child() and m["parallelism"].startswith("fan"):
         # without the ladder (DNN_LADDER=0): the literal grid measured in-process too
         u = measure(a, spec, n, world, dev, "uniform")
         uniform = {**(uniform or {}), "value": u["value"], "ms_per_step": u["ms_per_step"],
                    "parallelism": u["parallelism"], "layer_distribution": u["layer_distribution"],
                    "transport": u["transport"], "rccl_plan": u["rccl_plan"]}
     dp_only = None
-    if world > 1 and not a.no_dp_compare and not m["parallelism"].startswith(("dp", "tp")):
+    if a.full and world > 1 and not a.no_dp_compare and \
+            not m["parallelism"].startswith(("dp", "tp")):
         d = measure(a, spec, n, world, dev, f"dp{n}")
         dp_only = {k: d[k] for k in ("value", "ms_per_step", "parallelism", "global_batch",
                                      "transport", "native_step", "dp_reduce")}

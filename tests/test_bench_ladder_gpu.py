@@ -2,9 +2,9 @@
 launched by torch.distributed.run exactly as the driver launches bench.py. Rung 1 hangs on
 rank 0 (the first-step watchdog ends it), rung 2 crashes on rank 1 (rank 0's child is killed
 by its supervisor), rung 3 measures -- and rank 0 still prints ONE JSON line, with the
-attempts listed, followed by the data-parallel comparison run the same way. (The literal
-uniform grid: at N = 2 the planner's default is a co-located fan layout, whose own rungs
-tests/test_fan_gpu.py covers.)"""
+attempts listed, followed (--full) by the data-parallel comparison run the same way. (The
+literal uniform grid: at N = 2 the planner's default is a co-located fan layout, whose own
+rungs tests/test_fan_gpu.py covers.)"""
 import json
 import os
 import socket
@@ -37,7 +37,7 @@ def test_bench_ladder_survives_hang_and_crash(tmp_path):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2048",
-                        "--parallelism", "uniform"],
+                        "--parallelism", "uniform", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=None, text=True, timeout=280,
                        cwd=ROOT)  # stderr streams (run with -s): the attempts' progress
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

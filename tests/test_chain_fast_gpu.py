@@ -482,16 +482,24 @@ def _persistent_softmax_body(st, dev, K, N, n_out):
 
     g = torch.Generator().manual_seed(5)
     x = (torch.randn(8, K, generator=g) * 0.5).to(torch.bfloat16).to(dev)
+    # The torch references come first and the comparisons last: the launch ends by itself after
+    # 5 s without a request (idle), and a process's first torch GEMM loads its BLAS library,
+    # which on a cold machine can take longer than that -- between two requests it would let
+    # the kernel leave before the next one is fed.
+    sizes = (1, 8, 3)
+    refs = [torch.softmax(x[:rows].float() @ st.w[:n_out].float().t() + st.b[:n_out], dim=1)
+            for rows in sizes]
+    torch.cuda.current_stream(dev).synchronize()
     assert st.launch(0) == 1
-    for seq, rows in enumerate((1, 8, 3), start=1):
+    got = []
+    for seq, rows in enumerate(sizes, start=1):
         st.feed(seq, x[:rows])
-        hdr, out = st.wait_out(seq)
-        z = x[:rows].float() @ st.w[:n_out].float().t() + st.b[:n_out]
-        ref = torch.softmax(z, dim=1)
-        assert hdr == [0, rows]
-        torch.testing.assert_close(out[:rows, :n_out], ref, atol=1e-5, rtol=1e-4)
+        got.append(st.wait_out(seq))
         st.f_ack[0] = seq
     st.ctl[0] = 1
     st.s.synchronize()
+    for rows, ref, (hdr, out) in zip(sizes, refs, got):
+        assert hdr == [0, rows]
+        torch.testing.assert_close(out[:rows, :n_out], ref, atol=1e-5, rtol=1e-4)
     st.n.host_free(st.hp)
     st.n.stream_destroy(st.s_ptr)

@@ -209,29 +209,58 @@ def test_concurrent_requests_through_rank_chain(model_files, tmp_path):
         _stop(p)
 
 
-REF_CLIENT = "/root/reference/src/run_grpc_inference.py"
+# One batch request exactly as the ORIGINAL client puts it on the wire: the bytes its generated
+# dist_nn_pb2 stubs serialised for Matrix{Row{values}} with 32 rows of 784 values in [0, 1)
+# (recorded once from the reference's run_grpc_inference.py stubs; data only).
+GOLDEN_REQUEST = os.path.join(ROOT, "tests", "golden", "reference_client_request.bin")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CLIENT), reason="reference checkout not present")
 @pytest.mark.parametrize("mode", ["local", "ranks", "workers"])
-def test_unmodified_reference_client_interop(model_files, tmp_path, mode):
-    """The ORIGINAL client (/root/reference/src/run_grpc_inference.py with its own generated
-    dist_nn_pb2 / dist_nn_pb2_grpc stubs: Matrix{Row{values}} on
-    /grpc_dist_nn.LayerService/Process) runs unmodified against our ingress. It is executed
-    read-only (-B, no bytecode written into the reference tree)."""
-    cfg, inp, x, y = model_files
+def test_reference_client_wire_bytes_interop(model_files, tmp_path, mode):
+    """The original client's recorded request bytes, sent the way that client sends them (one
+    persistent channel with unlimited message sizes, a unary call on
+    /grpc_dist_nn.LayerService/Process per batch, no codec of ours on the client side), are
+    served by our ingress, and the raw reply parses with the stock protobuf classes of the
+    reference's schema -- what its generated stubs do -- into the fp64 forward's answers."""
+    from docker_dist_nn_amd.serve import proto
+
+    cfg, inp, _, _ = model_files
+    with open(GOLDEN_REQUEST, "rb") as f:
+        request = f.read()
+    sent = proto.Matrix()
+    sent.ParseFromString(request)
+    x = np.array([list(r.values) for r in sent.rows])
+    assert x.shape == (32, 784)
+    ref = model_forward(load_model_config(str(cfg)).layers, x)
     port = _port()
     p = _start(cfg, inp, port, mode, tmp_path)
     try:
-        r = subprocess.run([sys.executable, "-B", REF_CLIENT, "--inputs", str(inp),
-                            "--port", str(port), "--batch-size", "100", "--timeout", "30"],
-                           capture_output=True, text=True, timeout=180, cwd=str(tmp_path),
-                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-        log = r.stdout + r.stderr
-        assert "Batch 3/3 completed" in log, log
-        n = int(log.split("Correct predictions: ")[1].split(" ")[0])
-        assert n >= 290 and "out of 300" in log, log
-        assert "Inference process completed." in log
+        ch = grpc.insecure_channel(f"127.0.0.1:{port}",
+                                   options=[("grpc.max_send_message_length", -1),
+                                            ("grpc.max_receive_message_length", -1)])
+        grpc.channel_ready_future(ch).result(timeout=15)
+        call = ch.unary_unary("/grpc_dist_nn.LayerService/Process")  # raw bytes both ways
+        # the first stage listens before the later ones do (workers mode); a client process
+        # takes longer to start than that, so poll until the chain forwards
+        t0 = time.time()
+        while True:
+            try:
+                call(request, timeout=30)
+                break
+            except grpc.RpcError as e:
+                if e.code() != grpc.StatusCode.UNAVAILABLE or time.time() - t0 > 60:
+                    raise
+                time.sleep(0.2)
+        for _ in range(3):  # the client's batches reuse the one channel
+            reply = proto.Matrix()
+            reply.ParseFromString(call(request, timeout=30))
+            out = np.vstack([r.values for r in reply.rows])
+            assert out.shape == (32, 10)
+            # the client's count of correct predictions; the original asked for 290 of 300
+            # (bf16 vs fp64 may flip a near-tie): the same share of 32 rows is 31
+            assert int((out.argmax(1) == ref.argmax(1)).sum()) >= 31
+            np.testing.assert_allclose(out, ref, atol=2e-2)
+        ch.close()
     finally:
         _stop(p)
 

@@ -138,7 +138,7 @@ def test_bench_runs_the_fan_layout(tmp_path):
                         "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(root, "bench.py"),
                         "--gpus", "4", "--steps", "3", "--warmup", "1", "--batch", "4096",
-                        "--parallelism", "fan:3x3,1x1", "--no-dp-compare"],
+                        "--parallelism", "fan:3x3,1x1", "--full", "--no-dp-compare"],
                        env=env, stdout=subprocess.PIPE, stderr=None, text=True, timeout=280,
                        cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -192,7 +192,7 @@ def test_bench_colocated_fan_with_uniform_and_dp_measured(tmp_path):
                         "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(root, "bench.py"),
                         "--gpus", "4", "--steps", "3", "--warmup", "1", "--batch", "4096",
-                        "--parallelism", "fan:3x4,1x1@3"],
+                        "--parallelism", "fan:3x4,1x1@3", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=None, text=True, timeout=380,
                        cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

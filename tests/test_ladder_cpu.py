@@ -41,8 +41,12 @@ SCRIPT = textwrap.dedent("""
     sup = ladder.Supervisor(lambda r: [sys.executable, __file__], rank=rank, world=world,
                             stall=3.0)
     res, rung = sup.climb([ladder.Rung("a"), ladder.Rung("b"), ladder.Rung("c")])
-    print(json.dumps({{"rank": rank, "res": res, "rung": rung.name if rung else None,
-                      "attempts": sup.attempts}}), flush=True)
+    # both ranks share one pipe: the record and its newline go out in ONE write, so two
+    # ranks finishing together cannot interleave them (print() writes the newline separately
+    # when stdout is unbuffered)
+    sys.stdout.write(json.dumps({{"rank": rank, "res": res, "rung": rung.name if rung else None,
+                                 "attempts": sup.attempts}}) + "\\n")
+    sys.stdout.flush()
 """)
 
 
@@ -224,7 +228,9 @@ COMPARE_SCRIPT = textwrap.dedent("""
     out = sup.comparisons([("uniform_pipeline", [ladder.Rung("u1")]),
                            ("dp_only", [ladder.Rung("dp1")])], need_s=float({need}),
                           on_done=lambda k, e: seen.append(k))
-    print(json.dumps({{"rank": rank, "res": res, "out": out, "seen": seen}}), flush=True)
+    # one write per record, newline included (see SCRIPT)
+    sys.stdout.write(json.dumps({{"rank": rank, "res": res, "out": out, "seen": seen}}) + "\\n")
+    sys.stdout.flush()
 """)
 
 
