@@ -37,6 +37,8 @@ def _logical(a, b, layout_a, layout_b, M, N, Ktot):
 def _colsum_blocks(vals, out, rows_per):
     nb = vals.shape[0] // rows_per
     out[:nb, :vals.shape[1]] = vals[:nb * rows_per].reshape(nb, rows_per, -1).sum(1)
+    if vals.shape[0] % rows_per:  # partial edge tile: the kernels write its partial too
+        out[nb, :vals.shape[1]] = vals[nb * rows_per:].sum(0)
 
 
 def gemm(a, b, c, *, layout_a, layout_b, M, N, K, bias=None, aux=None, act=0, accumulate=False,

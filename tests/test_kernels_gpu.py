@@ -133,6 +133,13 @@ def test_gemm_random_bf16_out(dev, la, lb):
         ops.gemm(a, b, c, layout_a=la, layout_b=lb, M=M, N=N, K=K, bias=bias, act=act)
         ref = _logical(a, la, M, K) @ _logical(b, lb, N, K).t() + bias
         ref = {"linear": ref, "relu": ref.clamp_min(0), "sigmoid": torch.sigmoid(ref)}[act]
+        if act == "sigmoid":
+            # output in (0, 1): half a bf16 ulp there is at most 2^-9 = 1.95e-3; the fp32
+            # accumulation orders differ by < 1e-3 in z (K = 832 unit-variance terms), which the
+            # sigmoid's slope (<= 1/4) shrinks to < 2.5e-4. The activation arithmetic itself is
+            # pinned to 1 bf16 ulp of fp64 in tests/test_activation_epilogues_gpu.py.
+            torch.testing.assert_close(c.float(), ref, rtol=0, atol=2.5e-3)
+            continue
         torch.testing.assert_close(c.float(), ref, rtol=1.6e-2, atol=2e-2)
 
 

@@ -1,10 +1,13 @@
 """Fused classifier tail (csrc/kernels/mlp_tail.hip): one launch = fwd of layer L-2, fwd + softmax
 CE of layer L-1, dgrads of both. Its outputs must equal the four unfused kernels bit for bit
 (h3, dz4, dz3, dz2); the bias-gradient partials are grouped per workgroup, so their totals are
-compared with a tolerance, and against the fp32 CPU reference."""
+compared with a tolerance, and against the fp32 CPU reference. The unfused kernels share the
+activation code's blind spots, so the mixed-activation cases are also checked stage by stage
+against the fp64 oracle of tests/_act_oracle.py."""
 import pytest
 import torch
 
+import _act_oracle as ao
 from docker_dist_nn_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +28,8 @@ def _case(rows, k3, n3, n4, n_cls, seed):
     return x, w3, b3, w4, b4, labels
 
 
-def _run_tail(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act="relu"):
+def _run_tail(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act3="relu", act2=None):
+    act2 = act3 if act2 is None else act2
     rows, k3 = x.shape
     n3, n4 = w3.shape[0], w4.shape[0]
     nb = ops.tail_blocks(rows)
@@ -41,18 +45,27 @@ def _run_tail(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act="relu"):
                cs2=torch.full((nb, k3), 7.0, dtype=f32, device=dev))
     t = [a.to(dev) for a in (x, w3, b3, w4, b4, labels)]
     ops.mlp_tail(*t, out["h3"], out["dz4"], out["dz3"], out["dz2"], n_cls, scale,
-                 act3=act, act2=act, loss_part=out["loss"], correct=out["corr"],
+                 act3=act3, act2=act2, loss_part=out["loss"], correct=out["corr"],
                  cs4=out["cs4"], cs3=out["cs3"], cs2=out["cs2"])
     return out
 
 
-def _unfused(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act="relu"):
+def _unfused(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act3="relu", act2=None):
+    """The four unfused kernels. Their launch helpers take rows in multiples of 64: other row
+    counts run padded with zero rows labelled -1 (no loss, zero gradient, so every sum is that
+    of the real rows; a row's values do not depend on the row count) and are cut back."""
+    act2 = act3 if act2 is None else act2
+    real = x.shape[0]
+    if real % 64:
+        pad = 64 - real % 64
+        x = torch.cat([x, torch.zeros(pad, x.shape[1], dtype=x.dtype)])
+        labels = torch.cat([labels, torch.full((pad,), -1, dtype=labels.dtype)])
     rows, k3 = x.shape
     n3, n4 = w3.shape[0], w4.shape[0]
     x, w3, b3, w4, b4, labels = (a.to(dev) for a in (x, w3, b3, w4, b4, labels))
     bf, f32 = torch.bfloat16, torch.float32
     h3 = torch.empty(rows, n3, dtype=bf, device=dev)
-    ops.linear_fwd(x, w3, b3, h3, act=act)
+    ops.linear_fwd(x, w3, b3, h3, act=act3)
     nx = rows // ops.xent_tiles(rows, n4)[0]
     dz4 = torch.empty(rows, n4, dtype=bf, device=dev)
     loss = torch.zeros(nx, dtype=f32, device=dev)
@@ -61,12 +74,12 @@ def _unfused(dev, x, w3, b3, w4, b4, labels, n_cls, scale, act="relu"):
     ops.linear_fwd_xent(h3, w4, b4, dz4, labels, n_cls, scale, loss, corr, colsum=cs4)
     dz3 = torch.empty(rows, n3, dtype=bf, device=dev)
     cs3 = torch.zeros(rows // ops.dgrad_tiles(rows, n3, n4)[0], n3, dtype=f32, device=dev)
-    ops.linear_dgrad(dz4, w4, dz3, y_prev=h3, act_prev=act, colsum=cs3)
+    ops.linear_dgrad(dz4, w4, dz3, y_prev=h3, act_prev=act3, colsum=cs3)
     dz2 = torch.empty(rows, k3, dtype=bf, device=dev)
     cs2 = torch.zeros(rows // ops.dgrad_tiles(rows, k3, n3)[0], k3, dtype=f32, device=dev)
-    ops.linear_dgrad(dz3, w3, dz2, y_prev=x, act_prev=act, colsum=cs2)
-    return dict(h3=h3, dz4=dz4, dz3=dz3, dz2=dz2, loss=loss, corr=corr, cs4=cs4, cs3=cs3,
-                cs2=cs2)
+    ops.linear_dgrad(dz3, w3, dz2, y_prev=x, act_prev=act2, colsum=cs2)
+    return dict(h3=h3[:real], dz4=dz4[:real], dz3=dz3[:real], dz2=dz2[:real], loss=loss,
+                corr=corr, cs4=cs4, cs3=cs3, cs2=cs2)
 
 
 @pytest.mark.parametrize("rows,k3,n3,n4,n_cls,act", [(4096, 256, 128, 64, 10, "relu"),
@@ -90,6 +103,83 @@ def test_tail_equals_unfused_kernels(dev, monkeypatch, rows, k3, n3, n4, n_cls, 
     for k in ("cs4", "cs3", "cs2"):
         torch.testing.assert_close(got[k].sum(0), want[k].sum(0), rtol=1e-4, atol=1e-5)
     assert torch.all(got["cs4"][:, 16:] == 0)
+
+
+def _exact_case(rows, k3, n3, n4, n_cls, act2, seed):
+    """Operands for which x.w3^T + b3 is exact in fp32 (tests/_act_oracle.py): x a multiple of
+    1/16 -- inside (0, 1) where the layer below is a sigmoid, as it would produce it; >= 0 below
+    a ReLU -- w3 a multiple of 1/8, b3 of 1/4. w4 / b4 / labels as in _case."""
+    g = torch.Generator().manual_seed(seed)
+    if act2 == "sigmoid":
+        x = torch.randint(1, 16, (rows, k3), generator=g).float() / 16
+    else:
+        x = torch.randint(-8, 9, (rows, k3), generator=g).float() / 8
+        if act2 == "relu":
+            x = x.clamp_min(0)
+    w3 = torch.randint(-1, 2, (n3, k3), generator=g).float() / 8
+    b3 = torch.randint(-8, 9, (n3,), generator=g).float() * 0.25
+    w4 = torch.zeros(n4, n3)
+    w4[:n_cls] = torch.randn(n_cls, n3, generator=g) / n3 ** 0.5
+    b4 = torch.zeros(n4)
+    b4[:n_cls] = torch.randn(n_cls, generator=g) * 0.1
+    labels = torch.randint(0, n_cls, (rows,), generator=g, dtype=torch.int32)
+    labels[::7] = -1
+    return x.to(torch.bfloat16), w3.to(torch.bfloat16), b3, w4.to(torch.bfloat16), b4, labels
+
+
+def _assert_dgrad_fp64(name, got, dz, w, y, act):
+    """A dgrad output against fp64 evaluated from the kernel's OWN stored inputs: 2 bf16 ulps
+    (the single rounding of the result, and slack for a rounding boundary) plus an absolute
+    floor for the fp32 accumulation, whose error scales with the sum of |terms|, not with the
+    result: 4 x the largest |fp32 - fp64| of the CPU reference path (ops/reference.py) on the
+    same inputs. Returns the floor."""
+    from docker_dist_nn_amd.models.mlp import ACT_CODE
+    from docker_dist_nn_amd.ops import reference as ref
+
+    dz, w, y, got = (t.detach().cpu() for t in (dz, w, y, got))
+    want = ao.act_bwd(dz.double() @ w.double(), y, act)
+    f32 = ref.act_bwd(dz.float() @ w.float(), y.float(), ACT_CODE[act])
+    floor = 4.0 * float((f32.double() - want).abs().max())
+    excess = (got.double() - want).abs() - (2.0 * ao.bf16_ulp(want) + floor)
+    assert not torch.isnan(got.float()).any()
+    assert float(excess.max()) <= 0.0, (name, act, float(excess.max()), floor)
+    return floor
+
+
+GEOS = [(128, 64, 64, 10), (256, 64, 64, 10), (64, 128, 64, 10), (128, 128, 128, 16),
+        (256, 128, 64, 10)]
+
+
+@pytest.mark.parametrize(
+    "rows,k3,n3,n4,n_cls,act3,act2",
+    [(144, 64, 64, 64, 10, a3, a2) for a3 in ao.ACTS for a2 in ao.ACTS] +
+    [(144, *geo, a3, a2) for geo in GEOS for a3, a2 in (("sigmoid", "relu"), ("linear", "sigmoid"))] +
+    [(4096 + 48, 256, 128, 64, 10, "sigmoid", "relu")])
+def test_tail_mixed_activations_fp64(dev, monkeypatch, rows, k3, n3, n4, n_cls, act3, act2):
+    """act3 and act2 chosen independently (the engine passes them so): every pair, every
+    geometry of the generic 8-wave instantiation, 9 sixteen-row blocks (not a multiple of the 8
+    waves) and more blocks than workgroups. Bitwise against the unfused kernels, and stage by
+    stage against fp64: h3 from exact-product operands (1 bf16 ulp for sigmoid, bit-exact
+    otherwise), dz3 / dz2 from the kernel's own stored dz4 / dz3 and h3 / x."""
+    monkeypatch.setenv("DNN_BLAS", "0")
+    case = _exact_case(rows, k3, n3, n4, n_cls, act2, seed=rows + k3 + 2 * n3 + n_cls)
+    x, w3, b3, w4, b4, labels = case
+    scale = 1.0 / rows
+    got = _run_tail(dev, *case, n_cls, scale, act3, act2)
+    want = _unfused(dev, *case, n_cls, scale, act3, act2)
+    for k in ("h3", "dz4", "dz3", "dz2"):
+        assert torch.equal(got[k], want[k]), (k, (got[k].float() - want[k].float()).abs().max())
+    assert int(got["corr"].sum()) == int(want["corr"].sum())
+    torch.testing.assert_close(got["loss"].sum(), want["loss"].sum(), rtol=1e-5, atol=1e-3)
+    for k in ("cs4", "cs3", "cs2"):
+        torch.testing.assert_close(got[k].sum(0), want[k].sum(0), rtol=1e-4, atol=1e-5)
+    z3 = x.double() @ w3.double().t() + b3.double()
+    assert float(z3.abs().max()) <= 80.0
+    ao.assert_bf16_close(got["h3"], ao.act_fwd(z3, act3), 1 if act3 == "sigmoid" else 0, "h3")
+    assert bool((got["dz4"] != 0).any())
+    f3 = _assert_dgrad_fp64("dz3", got["dz3"], got["dz4"], w4, got["h3"], act3)
+    f2 = _assert_dgrad_fp64("dz2", got["dz2"], got["dz3"], w3, x, act2)
+    print(f"\nACTSTAT tail {rows}x{k3}x{n3} {act3}/{act2} floor dz3 {f3:.3e} dz2 {f2:.3e}")
 
 
 def test_tail_matches_cpu_reference(dev):
