@@ -374,18 +374,20 @@ int reduce_slabs(const float* src, long stride, int n_src, long n, float scale, 
 // sgd4 (one SGD step on 4 parameters) lives in common.hpp: shared with the GEMM epilogue.
 
 // One Adam / AdamW step on 4 elements (torch.optim semantics): shared by adam_kernel and the
-// fused reduction, so both paths produce the same bits.
+// fused reduction, so both paths produce the same bits. omb1 / omb2 = 1 - beta, rounded from
+// the DOUBLE difference on the host: 1.f - b2 in fp32 carries the rounding of b2 itself,
+// 2^-25 / (1 - b2) relative (1.3e-5 at b2 = 0.999), into every increment of v.
 __device__ __forceinline__ void adam4(float* __restrict__ p, f32x4_t gv, float* __restrict__ m,
                                       float* __restrict__ v, u16* __restrict__ shadow, float lr,
-                                      float b1, float b2, float eps, float wd, int decoupled,
-                                      float bc1, float bc2) {
+                                      float b1, float b2, float omb1, float omb2, float eps,
+                                      float wd, int decoupled, float bc1, float bc2) {
   f32x4_t pv = *(const f32x4_t*)p;
   if (decoupled) pv *= (1.f - lr * wd);
   else gv += wd * pv;
   f32x4_t mv = *(const f32x4_t*)m;
   f32x4_t vv = *(const f32x4_t*)v;
-  mv = b1 * mv + (1.f - b1) * gv;
-  vv = b2 * vv + (1.f - b2) * gv * gv;
+  mv = b1 * mv + omb1 * gv;
+  vv = b2 * vv + omb2 * gv * gv;
   *(f32x4_t*)m = mv;
   *(f32x4_t*)v = vv;
 #pragma unroll
@@ -398,6 +400,9 @@ __device__ __forceinline__ void adam4(float* __restrict__ p, f32x4_t gv, float* 
     *(bf16x4_t*)shadow = o;
   }
 }
+
+// 1 - beta for adam4: from the double beta where the caller gave it (> 0), else from the float.
+static float one_minus_beta(float b, double db) { return db > 0.0 ? (float)(1.0 - db) : 1.f - b; }
 
 template <int TY>
 __device__ __forceinline__ void reduce_block(const ReduceJob& jb, long blk, f32x4_t LDS_AS* red,
@@ -440,8 +445,8 @@ __device__ __forceinline__ void reduce_block(const ReduceJob& jb, long blk, f32x
           bc2 = (float)(1.0 / (1.0 - pow(sg.db2, tt)));
         }
         adam4(sg.master + off, t, sg.mom + off, sg.v + off,
-              sg.shadow ? sg.shadow + off : nullptr, lr, sg.b1, sg.b2, sg.eps, sg.wd,
-              sg.decoupled, bc1, bc2);
+              sg.shadow ? sg.shadow + off : nullptr, lr, sg.b1, sg.b2, sg.omb1, sg.omb2,
+              sg.eps, sg.wd, sg.decoupled, bc1, bc2);
       } else {
         sgd4(sg.master + off, t, sg.mom ? sg.mom + off : nullptr,
              sg.shadow ? sg.shadow + off : nullptr, lr, sg.mu, sg.wd);
@@ -501,6 +506,8 @@ int reduce_multi(const ReduceJob* job, int n_jobs, hipStream_t stream, const Fus
   FusedSgd sg{};
   if (sgd) {
     sg = *sgd;
+    sg.omb1 = one_minus_beta(sg.b1, sg.db1);
+    sg.omb2 = one_minus_beta(sg.b2, sg.db2);
     for (int k = 0; k < n_jobs; ++k)  // every output must lie in the flat gradient, 16-B aligned
       if (job[k].out < sg.grad_base || ((job[k].out - sg.grad_base) & 3)) return -1;
   }
@@ -544,8 +551,9 @@ int sgd_update(float* p, const float* g, float* mom, uint16_t* shadow, long n, f
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    u16* __restrict__ shadow, long n4, float lr,
-                                                   float b1, float b2, float eps, float wd,
-                                                   int decoupled, float bc1, float bc2,
+                                                   float b1, float b2, float omb1, float omb2,
+                                                   float eps, float wd, int decoupled, float bc1,
+                                                   float bc2,
                                                    const float* __restrict__ lr_dev,
                                                    const int* __restrict__ step_dev, double db1,
                                                    double db2) {
@@ -557,7 +565,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
     adam4(p + i * 4, *(const f32x4_t*)(g + i * 4), m + i * 4, v + i * 4,
-          shadow ? shadow + i * 4 : nullptr, lr, b1, b2, eps, wd, decoupled, bc1, bc2);
+          shadow ? shadow + i * 4 : nullptr, lr, b1, b2, omb1, omb2, eps, wd, decoupled, bc1,
+          bc2);
 }
 
 int adam_update(float* p, const float* g, float* m, float* v, uint16_t* shadow, long n, float lr,
@@ -566,7 +575,8 @@ int adam_update(float* p, const float* g, float* m, float* v, uint16_t* shadow, 
                 double db2) {
   if (n <= 0 || n % 4) return -1;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, shadow,
-                     n / 4, lr, b1, b2, eps, wd, decoupled, bc1, bc2, lr_dev, step_dev, db1, db2);
+                     n / 4, lr, b1, b2, one_minus_beta(b1, db1), one_minus_beta(b2, db2), eps, wd,
+                     decoupled, bc1, bc2, lr_dev, step_dev, db1, db2);
   return hipGetLastError() == hipSuccess ? 0 : -9;
 }
 

@@ -63,6 +63,7 @@ struct FusedSgd {
   const int* step_dev;
   double db1, db2;
   float bc1, bc2;
+  float omb1, omb2;  // 1 - beta of adam4: filled in by reduce_multi() from db1 / db2
 };
 // All jobs in one launch, each bitwise identical to reduce_slabs on the same inputs.
 // max_blocks > 0: at most that many workgroups, each looping over the launch's blocks (the

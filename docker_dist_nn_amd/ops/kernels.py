@@ -680,8 +680,10 @@ def linear_wgrad(dz, x, slabs, splits=1, accumulate=False, dzt=None, xt=None, up
     ``dzt`` / ``xt`` (bf16 [Np][R] / [Kp][R], written transposed by the producing GEMMs'
     epilogues): the contraction runs K-major on both operands (the forward's main loop,
     bench/layout_ab.py: 1.2x on 8192x8192 weights); same k order, same result bits.
-    ``upd`` (one split): the epilogue applies the SGD step to the layer's weights instead of
-    storing the gradient (ops.gemm), and writes the new bf16 weights transposed into ``wt``."""
+    ``upd`` (one split): the epilogue applies the SGD step to the layer's weights (ops.gemm) and
+    writes the new bf16 weights transposed into ``wt``. On the GPU the gradient itself is then
+    NOT stored: ``slabs`` is left untouched (it only supplies the row stride that master / mom /
+    shadow share). The CPU reference path does store it."""
     R, N = dz.shape
     K = x.shape[1]
     if upd is not None and (splits != 1 or accumulate):

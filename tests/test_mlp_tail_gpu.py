@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _act_oracle as ao
+import _loss_oracle as lo
 from docker_dist_nn_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -176,7 +177,11 @@ def test_tail_mixed_activations_fp64(dev, monkeypatch, rows, k3, n3, n4, n_cls, 
     z3 = x.double() @ w3.double().t() + b3.double()
     assert float(z3.abs().max()) <= 80.0
     ao.assert_bf16_close(got["h3"], ao.act_fwd(z3, act3), 1 if act3 == "sigmoid" else 0, "h3")
-    assert bool((got["dz4"] != 0).any())
+    z4, exact = lo.tail_logits(got["h3"], w4, b4, n_cls, strict=False)
+    if exact:  # then dz4 has an fp64 oracle (tests/_loss_oracle.py)
+        lo.assert_dz(got["dz4"], lo.xent_ref(z4, labels, scale), n4, what="dz4")
+    else:
+        assert bool((got["dz4"] != 0).any())
     f3 = _assert_dgrad_fp64("dz3", got["dz3"], got["dz4"], w4, got["h3"], act3)
     f2 = _assert_dgrad_fp64("dz2", got["dz2"], got["dz3"], w3, x, act2)
     print(f"\nACTSTAT tail {rows}x{k3}x{n3} {act3}/{act2} floor dz3 {f3:.3e} dz2 {f2:.3e}")
