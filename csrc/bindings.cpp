@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels/chain.hpp"
+#include "kernels/dense_loss.hpp"
 #include "kernels/elementwise.hpp"
 #include "kernels/gemm.hpp"
 #include "kernels/gemv.hpp"
@@ -230,6 +231,28 @@ PYBIND11_MODULE(_native, m) {
         py::arg("loss_part"), py::arg("correct"), py::arg("stream"), py::arg("colsum") = 0,
         py::arg("ld_colsum") = 0);
   m.def("softmax_xent_blocks", &dnn::softmax_xent_blocks);
+  m.def("dense_loss",
+        [](uintptr_t z, long ld_z, uintptr_t t, long ld_t, uintptr_t row_ok, uintptr_t dz,
+           long ld_dz, int rows, int n_out, int width, int loss, int act, float scale,
+           uintptr_t loss_part, uintptr_t colsum, long ld_colsum, uintptr_t stream) {
+          launch(
+              "dense_loss",
+              [=](hipStream_t s, const dnn::Program& R) {
+                return dnn::dense_loss(R.fix(P<const float>(z)), ld_z,
+                                       R.fix(P<const uint16_t>(t)), ld_t,
+                                       R.fix(P<const int>(row_ok)), R.fix(P<uint16_t>(dz)),
+                                       ld_dz, rows, n_out, width, loss, act, scale,
+                                       R.fix(P<float>(loss_part)), R.fix(P<float>(colsum)),
+                                       ld_colsum, s);
+              },
+              stream);
+        },
+        py::arg("z"), py::arg("ld_z"), py::arg("t"), py::arg("ld_t"), py::arg("row_ok"),
+        py::arg("dz"), py::arg("ld_dz"), py::arg("rows"), py::arg("n_out"), py::arg("width"),
+        py::arg("loss"), py::arg("act"), py::arg("scale"), py::arg("loss_part"),
+        py::arg("colsum"), py::arg("ld_colsum"), py::arg("stream"));
+  m.def("dense_loss_row_blocks", &dnn::dense_loss_row_blocks);
+  m.def("dense_loss_col_chunks", &dnn::dense_loss_col_chunks);
   m.def(
       "mlp_tail",
       [](uintptr_t x, long ldx, uintptr_t w3, long ldw3, uintptr_t b3, uintptr_t w4, long ldw4,

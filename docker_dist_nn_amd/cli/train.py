@@ -4,7 +4,8 @@ docker_dist_nn_amd.cli.train ...`` (one rank per GPU, PP x DP).
 
 This is the distributed version of the reference's centralized recipes
 (/root/reference/scripts/generate_mnist_pytorch.py:35-52, notebook …ipynb:274-285): softmax
-cross-entropy on the last layer's logits, mini-batch optimizer steps; the trained weights are
+cross-entropy on the last layer's logits (or, ``--loss mse | bce``, a dense-target loss for
+regression / multi-label / autoencoder heads), mini-batch optimizer steps; the trained weights are
 exported in the reference's neuron-JSON format with the notebook's ``inference_metrics``
 block (accuracy / weighted precision, recall, F1 / latency, …ipynb:493-506).
 """
@@ -54,7 +55,75 @@ def _batches(x, y, rows: int, kp: int, device, epoch_seed: int):
         yield xb.to(device), yb.to(device), len(idx)
 
 
-def evaluate(ws, bs, acts, x, y, device, batch: int = 65536) -> dict:
+def _dense_batches(x, y, t, rows: int, kp: int, np_: int, device, epoch_seed: int):
+    """_batches plus the bf16 target rows [rows][np_] (same order). ``t is x`` (--targets input):
+    the padded input batch itself is the target batch (bound zero-copy by the caller). Rows
+    past the data, and rows whose class label is < 0, are padding (validity -1)."""
+    n = x.shape[0]
+    order = np.random.default_rng(epoch_seed).permutation(n)
+    for (xb, yb, m), s in zip(_batches(x, y, rows, kp, device, epoch_seed), range(0, n, rows)):
+        if t is x and kp == np_:
+            tb = xb
+        else:
+            idx = order[s:s + rows]
+            tb = torch.zeros(rows, np_, dtype=torch.bfloat16)
+            tb[:len(idx), :t.shape[1]] = torch.from_numpy(t[idx]).to(torch.bfloat16)
+            tb = tb.to(device)
+        yield xb, torch.clamp(yb, max=0), tb, m
+
+
+def apply_loss_args(spec, a, from_config: bool):
+    """The model ``--loss`` trains: a widths model (``--model``) under a dense loss gets the
+    output activation ``--out-activation`` (default: linear for mse, sigmoid for bce) instead of
+    the softmax of a classifier; a JSON model keeps the activation it declares."""
+    from ..models.mlp import MLPSpec
+
+    loss = getattr(a, "loss", "softmax_ce")
+    act = getattr(a, "out_activation", None)
+    if act is None and loss != "softmax_ce" and not from_config and \
+            spec.layers[-1].activation == "softmax":
+        act = "linear" if loss == "mse" else "sigmoid"
+        log.info(f"--loss {loss}: output activation {act} (see --out-activation)")
+    if act is not None and act != spec.layers[-1].activation:
+        if from_config:
+            raise ValueError("--out-activation applies to --model widths; a JSON model "
+                             "declares its own activations")
+        spec = MLPSpec.from_widths(spec.widths, hidden_act=spec.layers[0].activation
+                                   if len(spec.layers) > 1 else "relu", out_act=act,
+                                   name=spec.name)
+    return spec, loss
+
+
+def dense_targets(x: np.ndarray, y: np.ndarray, mode: str, out_dim: int) -> np.ndarray:
+    """Dense target rows of ``--targets``: ``onehot`` of the class labels (a label < 0 gives an
+    all-zero row), or ``input`` (target = input, autoencoder)."""
+    if mode == "input":
+        if x.shape[1] != out_dim:
+            raise ValueError(f"--targets input needs out_dim == in_dim, got {out_dim} and "
+                             f"{x.shape[1]}")
+        return x
+    if mode != "onehot":
+        raise ValueError(f"--targets must be onehot | input, got {mode!r}")
+    if int(y.max(initial=-1)) >= out_dim:
+        raise ValueError(f"label {int(y.max())} does not fit {out_dim} output columns")
+    t = np.zeros((len(y), out_dim), dtype=np.float32)
+    ok = y >= 0
+    t[np.nonzero(ok)[0], y[ok]] = 1.0
+    return t
+
+
+def mean_dense_loss(out: np.ndarray, t: np.ndarray, loss: str) -> float:
+    """Mean (over rows and columns) loss of served outputs ``out`` = act(z) against ``t``."""
+    out, t = out.astype(np.float64), t.astype(np.float64)
+    if loss == "mse":
+        return float(np.mean((out - t) ** 2))
+    eps = 1e-12  # bce from the served probabilities
+    return float(np.mean(-(t * np.log(np.clip(out, eps, None)) +
+                           (1.0 - t) * np.log(np.clip(1.0 - out, eps, None)))))
+
+
+def evaluate(ws, bs, acts, x, y, device, batch: int = 65536, loss: str = "softmax_ce",
+             targets: Optional[np.ndarray] = None) -> dict:
     from ..config import LayerWeights
     from ..engine.inference import InferenceEngine
     from ..metrics import classification_report
@@ -64,6 +133,10 @@ def evaluate(ws, bs, acts, x, y, device, batch: int = 65536) -> dict:
     t0 = time.time()
     out = eng.predict(x)
     dt = time.time() - t0
+    if loss != "softmax_ce":  # a dense-target head has no classes: report the mean loss
+        rep = {"loss": mean_dense_loss(np.asarray(out), targets, loss), "loss_name": loss}
+        rep.update(total_latency_sec=dt, avg_latency_per_sample_sec=dt / max(1, len(x)))
+        return rep
     rep = classification_report(y, out.argmax(1), n_classes=out.shape[1])
     rep.update(total_latency_sec=dt, avg_latency_per_sample_sec=dt / max(1, len(x)))
     return rep
@@ -74,24 +147,32 @@ def train_model(mc, examples, a, distribution, random_init: bool):
     from ..engine import OptimConfig, Trainer
     from ..metrics import MetricsWriter
 
-    spec = mc.spec()
+    spec, loss_name = apply_loss_args(mc.spec(), a, from_config=True)
+    dense = loss_name != "softmax_ce"
     dev = torch.device("cpu") if getattr(a, "device", "auto") == "cpu" or \
         not torch.cuda.is_available() else torch.device("cuda", 0)
     x, y, src = prepare_data(examples, a.synthetic, spec.in_dim, a.seed)
+    t = dense_targets(x, y, getattr(a, "targets", "onehot"), spec.out_dim) if dense else None
     pp = sum(1 for d in distribution if d)
     tr = Trainer(spec, micro_batch=a.micro_batch, num_micro=a.num_micro_batches, pp=pp,
                  distribution=distribution, schedule=a.schedule,
                  optim=OptimConfig(name=a.optimizer, lr=a.lr, momentum=a.momentum),
-                 device=dev, seed=a.seed)
+                 device=dev, seed=a.seed, loss=loss_name)
     if not random_init:
         tr.load_weights([L.weight for L in mc.layers], [L.bias for L in mc.layers])
     mw = MetricsWriter(getattr(a, "metrics", None))
     rows = a.micro_batch * a.num_micro_batches
     kp = tr.stages[0].x_in.shape[1]
     step, t0, loss = 0, time.time(), None
+    np_ = tr.stages[-1].dz[-1].shape[1]
     for ep in range(max(1, a.epochs)):
-        for xb, yb, n in _batches(x, y, rows, kp, dev, a.seed + ep):
-            tr.set_batch(xb, yb)
+        batches = _dense_batches(x, y, t, rows, kp, np_, dev, a.seed + ep) if dense else \
+            ((xb, yb, None, n) for xb, yb, n in _batches(x, y, rows, kp, dev, a.seed + ep))
+        for xb, yb, tb, n in batches:
+            if dense:
+                tr.set_batch(xb, yb, zero_copy=tb is xb, targets=tb)
+            else:
+                tr.set_batch(xb, yb)
             tr.step()
             step += 1
             if step % 50 == 0 or (a.steps and step >= a.steps):
@@ -108,7 +189,8 @@ def train_model(mc, examples, a, distribution, random_init: bool):
     ww = tr.local_weights()
     ws = [ww[i][0] for i in range(len(spec.layers))]
     bs = [ww[i][1] for i in range(len(spec.layers))]
-    metrics = evaluate(ws, bs, [l.activation for l in spec.layers], x, y, dev)
+    metrics = evaluate(ws, bs, [l.activation for l in spec.layers], x, y, dev, loss=loss_name,
+                       targets=t)
     report = {"steps": step, "final_loss": loss, "train_seconds": elapsed,
               "samples_per_s": step * rows / max(elapsed, 1e-9), "data": src,
               "inference_metrics": metrics}
@@ -129,6 +211,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd")
     ap.add_argument("--momentum", type=float, default=0.0)
     ap.add_argument("--weight-decay", type=float, default=0.0)
+    ap.add_argument("--loss", choices=["softmax_ce", "mse", "bce"], default="softmax_ce",
+                    help="softmax cross-entropy on class labels, or a dense-target loss: mse "
+                         "(output linear | relu | sigmoid) or bce (sigmoid output, from logits)")
+    ap.add_argument("--targets", choices=["onehot", "input"], default="onehot",
+                    help="dense targets of --loss mse | bce: one-hot class labels, or the input "
+                         "row itself (autoencoder: out_dim == in_dim)")
+    ap.add_argument("--out-activation", choices=["softmax", "linear", "relu", "sigmoid"],
+                    default=None, help="output activation of a --model widths model (default "
+                    "softmax; under --loss mse: linear, --loss bce: sigmoid)")
     ap.add_argument("--micro-batch", type=int, default=4096)
     ap.add_argument("--num-micro-batches", type=int, default=1)
     ap.add_argument("--pp", type=int, default=0, help="pipeline stages (0 = planner)")
@@ -170,6 +261,8 @@ def main(argv: Optional[list[str]] = None) -> int:
     rank = int(os.environ.get("RANK", "0"))
     mc = load_model_config(a.config) if a.config else None
     spec = mc.spec() if mc else (NAMED_MODELS.get(a.model) or MLPSpec.parse(a.model))
+    spec, loss_name = apply_loss_args(spec, a, from_config=mc is not None)
+    dense = loss_name != "softmax_ce"
     if a.device == "cpu" or not torch.cuda.is_available():
         dev = torch.device("cpu")
     else:
@@ -192,7 +285,8 @@ def main(argv: Optional[list[str]] = None) -> int:
     tr = Trainer(spec, micro_batch=a.micro_batch, num_micro=a.num_micro_batches, pp=pp, dp=dp,
                  distribution=dist_, schedule=a.schedule, mesh=mesh, device=dev, seed=a.seed,
                  optim=OptimConfig(name=a.optimizer, lr=a.lr, momentum=a.momentum,
-                                   weight_decay=a.weight_decay), dp_reduce=a.dp_reduce)
+                                   weight_decay=a.weight_decay), dp_reduce=a.dp_reduce,
+                 loss=loss_name)
     start_step = 0
     if a.resume and a.checkpoint_dir and os.path.exists(os.path.join(a.checkpoint_dir, "meta.json")):
         # any layout: weights AND optimizer state are stored per layer (re-partition is exact)
@@ -210,6 +304,9 @@ def main(argv: Optional[list[str]] = None) -> int:
     shard = slice(replica, None, dp)  # each replica sees a disjoint strided shard
     x, y = x[shard], y[shard]
     kp = (spec.in_dim + 63) // 64 * 64  # the FIRST stage's padded input width (on every rank)
+    np_ = (spec.out_dim + 63) // 64 * 64  # the LAST stage's padded output width
+    t = dense_targets(x, y, a.targets, spec.out_dim) if dense else None
+    first_loss = None
     mw = MetricsWriter(a.metrics.format(rank=rank) if a.metrics else None, rank)
     prof = StepProfiler(tr.executor, rank, enabled=bool(a.trace))
     if a.watchdog is None:  # on by default wherever a peer can hang us
@@ -251,13 +348,21 @@ def main(argv: Optional[list[str]] = None) -> int:
         if (ep + 1) * per_epoch <= start_step:
             continue  # epoch fully consumed before the checkpoint
         skip = max(0, start_step - ep * per_epoch)
-        for bi, (xb, yb, _) in enumerate(_batches(x, y, rows, kp, dev, a.seed + ep)):
+        batches = _dense_batches(x, y, t, rows, kp, np_, dev, a.seed + ep) if dense else \
+            ((xb, yb, None, n) for xb, yb, n in _batches(x, y, rows, kp, dev, a.seed + ep))
+        for bi, (xb, yb, tb, _) in enumerate(batches):
             if bi < skip:
                 continue  # resume: the batch order is seeded per epoch, skip what was trained
             faults.maybe_inject(sid, step, tr.stages[0])
-            tr.set_batch(xb if tr.first else None, yb if tr.last else None)
+            if dense:  # --targets input: the input batch is bound in place as the target batch
+                tr.set_batch(xb if tr.first else None, yb if tr.last else None,
+                             zero_copy=tb is xb, targets=tb if tr.last else None)
+            else:
+                tr.set_batch(xb if tr.first else None, yb if tr.last else None)
             tr.step()
             step += 1
+            if dense and first_loss is None and tr.last is not None:
+                first_loss = tr.loss()
             if wd:
                 wd.beat(f"step {step}")
             if a.trace:
@@ -307,8 +412,11 @@ def main(argv: Optional[list[str]] = None) -> int:
                               [ww[i][1] for i in range(len(spec.layers))],
                               [l.activation for l in spec.layers], layer_distribution=dist_)
     if rank == 0:
-        print(json.dumps({"steps": step, "samples_per_s": rate, "loss": tr.loss(),
-                          "parallelism": f"pp{pp}dp{dp}", "data": src}), flush=True)
+        out = {"steps": step, "samples_per_s": rate, "loss": tr.loss(),
+               "parallelism": f"pp{pp}dp{dp}", "data": src}
+        if dense:
+            out.update(loss_name=loss_name, targets=a.targets, first_loss=first_loss)
+        print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
     return 0

@@ -71,13 +71,18 @@ class FanTrainer(Trainer):
                  num_micro: int, optim: Optional[OptimConfig] = None,
                  device: Optional[torch.device] = None, seed: int = 0,
                  dp_reduce: str = "allreduce", native_exec: Optional[bool] = None,
-                 hop_cost: float = 0.0, ipc_rehearsal: bool = False):
+                 hop_cost: float = 0.0, ipc_rehearsal: bool = False,
+                 loss: str = "softmax_ce"):
         """``ipc_rehearsal`` (one-GPU tests: ranks sharing a GPU over gloo): set up the IPC
         transport (``self.ipc_pipe``) whatever the backend, for a test that runs the IPC fan
         plan through the plan interpreter; the Python executor keeps the gloo FanPipe.
         ``ipc_rehearsal="native"``: the IPC fan plan as the rank's real StepPlan (eager or
         captured, Trainer.capture) -- layouts without replicated stages only, since a DP
         group's buckets are RCCL calls and RCCL runs one rank per GPU."""
+        if loss != "softmax_ce":
+            raise ValueError(f"fan layouts train with loss='softmax_ce' only, got {loss!r}: "
+                             "the dense losses (mse | bce) run on Trainer (pp x dp layouts)")
+        self.loss_name = loss
         if sum(layout.dist) != len(spec.layers):
             raise ValueError(f"fan layout {layout.dist} does not cover {len(spec.layers)} layers")
         layout.check_directions(num_micro)

@@ -16,7 +16,9 @@ This is the MI355X replacement of the reference's stage worker
 Per layer the compute is three fused gfx950 kernels: forward GEMM with bias+activation
 epilogue, dgrad GEMM whose epilogue applies the previous layer's activation derivative (read
 from the stored activation -- no mask tensor), and the wgrad GEMM. The last layer of the last
-stage writes fp32 logits and runs the fused softmax-cross-entropy kernel.
+stage writes fp32 logits and runs the fused softmax-cross-entropy kernel -- or, with
+``loss="mse" | "bce"``, fp32 pre-activations and the dense-target loss kernel (ops.dense_loss)
+against a bf16 target matrix.
 """
 from __future__ import annotations
 
@@ -396,9 +398,14 @@ class Stage:
                  num_micro: int, device: torch.device, global_batch: Optional[int] = None,
                  optim: Optional[OptimConfig] = None, wgrad: str = "batched",
                  stage_index: int = 0, num_stages: int = 1, wgrad_algo: Optional[str] = None,
-                 dp_shard: Optional[tuple[int, int]] = None):
+                 dp_shard: Optional[tuple[int, int]] = None, loss: str = "softmax_ce"):
         if not 0 <= layer_start < layer_end <= len(spec.layers):
             raise ValueError("bad layer range")
+        # loss of the last stage: softmax cross-entropy against int32 class labels (default),
+        # or a dense-target loss (ops.dense_loss: mse | bce) against a bf16 target matrix
+        if loss != "softmax_ce":
+            ops.check_dense_loss(loss, spec.layers[-1].activation)
+        self.loss = loss
         if micro_batch <= 0 or micro_batch % 64:
             raise ValueError("micro_batch must be a positive multiple of 64 (MFMA row tiles); "
                              "pad the batch with label -1 rows")
@@ -431,7 +438,8 @@ class Stage:
         # the last layer's softmax-CE is fused into its GEMM epilogue when the padded class
         # count is one 64/128-wide tile: logits then never exist in memory
         gl = self.geoms[-1]
-        self.fused_xent = (self.last and gl.np_ in (64, 128) and
+        self.dense = self.last and self.loss != "softmax_ce"
+        self.fused_xent = (self.last and not self.dense and gl.np_ in (64, 128) and
                            switches.get("DNN_FUSED_XENT") == "1")
         self.acts: list[torch.Tensor] = []  # output of local layer i
         for i, g in enumerate(self.geoms):
@@ -471,6 +479,10 @@ class Stage:
         self.dx_send = None if self.first else torch.zeros(R, g0.kp, dtype=bf, device=dev)
         self.labels = torch.full((R,), -1, dtype=torch.int32, device=dev) if self.last else None
         self.labels_buf = self.labels  # owned buffer; ``labels`` may alias a dataset slice
+        # dense-target loss: bf16 targets [rows][Np] (``labels`` is then only the row-validity
+        # vector, -1 = padding row)
+        self.targets = torch.zeros(R, gl.np_, dtype=bf, device=dev) if self.dense else None
+        self.targets_buf = self.targets  # owned buffer; ``targets`` may alias a dataset slice
         # Narrow classifier tail (csrc/kernels/mlp_tail.hip): the forward of the last two
         # layers, the softmax CE and both of their dgrads run as ONE kernel inside the last
         # layer's forward; the second-to-last layer's forward and both dgrads are then no-ops.
@@ -502,7 +514,10 @@ class Stage:
         else:
             self.xent_per_micro = (self.mb // ops.xent_tiles(self.mb, gl.np_)[0]
                                    if self.fused_xent else ops.xent_blocks(self.mb))
-        self.loss_part = torch.zeros(self.xent_per_micro * self.nm, dtype=f32, device=dev)
+        # loss partials per micro-batch: one per row block, times the dense loss's column chunks
+        self.loss_chunks = ops.dense_loss_col_chunks(gl.np_) if self.dense else 1
+        self.loss_part = torch.zeros(self.xent_per_micro * self.loss_chunks * self.nm, dtype=f32,
+                                     device=dev)
         # per-block correct counts, written (not accumulated) by the loss kernels
         self.correct = torch.zeros(self.xent_per_micro * self.nm, dtype=torch.int32, device=dev)
         # wgrad geometry: batched = one GEMM over all rows; per_micro = one per micro-batch
@@ -545,7 +560,7 @@ class Stage:
         self._recording = False
         self._has_w = False
         self._o_native = False  # "O" recorded (device-side lr / step)
-        self._rx = self._rl = None
+        self._rx = self._rl = self._rt = None
         self.boundary = "bf16"
         self._fp8_next = self._fp8_prev = False
 
@@ -669,6 +684,14 @@ class Stage:
                                 self.loss_part[k:k + self.xent_per_micro],
                                 self.correct[k:k + self.xent_per_micro],
                                 colsum=self._bpart(i, j))
+        elif self.dense and i == len(self.geoms) - 1:
+            ops.linear_fwd(x, p.wbf(i), p.b32(i), y, act="linear")  # fp32 pre-activations
+            k = j * self.xent_per_micro * self.loss_chunks
+            ops.dense_loss(y, self.targets[r], self.dz[i][r], self.n_cls,
+                           1.0 / self.global_batch, self.loss, g.spec.activation,
+                           row_ok=self.labels[r],
+                           loss_part=self.loss_part[k:k + self.xent_per_micro * self.loss_chunks],
+                           colsum=self._bpart(i, j))
         elif self.last and i == len(self.geoms) - 1:
             ops.linear_fwd(x, p.wbf(i), p.b32(i), y, act="linear")  # fp32 logits
             k = j * self.xent_per_micro
@@ -973,8 +996,9 @@ class Stage:
         F{j} / B{j} per micro-batch, W{i} / W (batched wgrad), FIN{i} / FIN (gradient
         reduction) and O (SGD update). Afterwards forward/backward/... replay their segment
         from C++ (one Python call per schedule op instead of one per kernel). The first
-        stage's input and the last stage's labels are relocatable regions, so zero-copy
-        batches (bind_input / bind_labels) work without re-recording. The Python bodies stay
+        stage's input and the last stage's labels (and dense targets) are relocatable regions,
+        so zero-copy batches (bind_input / bind_labels / bind_targets) work without
+        re-recording. The Python bodies stay
         the reference path (CPU, per-micro wgrad, Adam)."""
         nat = native()
         prog = nat.Program()
@@ -985,6 +1009,10 @@ class Stage:
                     if self.first else None)
         self._rl = (prog.region(self.labels_buf.data_ptr(), self.labels_buf.numel() * 4)
                     if self.labels is not None else None)
+        if self.targets is not None:
+            self.targets = self.targets_buf
+        self._rt = (prog.region(self.targets_buf.data_ptr(), self.targets_buf.numel() * 2)
+                    if self.targets is not None else None)
         # DNN_H0_DOUBLE: the layer-0 activation alternates between two buffers from step to
         # step (a relocatable region re-based by flip_h0), so the next step's layer-0 forward
         # never has to wait for this step's side-stream weight gradient that reads it
@@ -1106,16 +1134,32 @@ class Stage:
         if self._prog is not None and self._rl is not None:
             self._prog.rebase(self._rl, y.data_ptr())
 
+    def bind_targets(self, t: torch.Tensor) -> None:
+        """Dense loss: the last stage reads the bf16 targets ``t`` ([rows][Np], the row stride
+        of ``targets_buf``) in place from now on."""
+        self.targets = t
+        if self._prog is not None and self._rt is not None:
+            self._prog.rebase(self._rt, t.data_ptr())
+
     # convenience: a whole step when this stage holds the entire model ----------------------
-    def set_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
+    def set_batch(self, x: torch.Tensor, labels: Optional[torch.Tensor],
+                  targets: Optional[torch.Tensor] = None) -> None:
         self.bind_input(self.x_buf)  # never write through an alias of the caller's dataset
         self.x_in.copy_(x)
         if self.labels is not None:
             self.bind_labels(self.labels_buf)
-            self.labels.copy_(labels)
+            if labels is None and self.dense:
+                self.labels.zero_()  # every row valid
+            else:
+                self.labels.copy_(labels)
+        if self.dense:
+            if targets is None:
+                raise ValueError(f"loss {self.loss!r} needs dense targets")
+            self.bind_targets(self.targets_buf)
+            self.targets[:, :targets.shape[1]].copy_(targets)
 
     def loss_sum(self) -> float:
-        """Sum of per-row CE losses of the last step (fixed-order fp64 host sum)."""
+        """Sum of per-row losses of the last step (fixed-order fp64 host sum)."""
         return float(self.loss_part.detach().cpu().double().sum())
 
     def flops_per_step(self) -> float:

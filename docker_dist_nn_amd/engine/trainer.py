@@ -70,7 +70,14 @@ class Trainer:
                  device: Optional[torch.device] = None, seed: int = 0,
                  mesh: Optional[Mesh] = None, wgrad: Optional[str] = None,
                  native_exec: Optional[bool] = None, boundary: str = "bf16",
-                 dp_reduce: str = "allreduce"):
+                 dp_reduce: str = "allreduce", loss: str = "softmax_ce"):
+        # loss: "softmax_ce" (int32 class labels) or a dense-target loss against a bf16 target
+        # matrix -- "mse" (last activation linear | relu | sigmoid) or "bce" (sigmoid)
+        if loss != "softmax_ce":
+            from .. import ops
+
+            ops.check_dense_loss(loss, spec.layers[-1].activation)
+        self.loss_name = loss
         self.spec = spec
         self.mesh = mesh
         self.device = device or (torch.device("cuda", torch.cuda.current_device())
@@ -102,7 +109,7 @@ class Trainer:
         mk = lambda p: Stage(spec, p.layer_start, p.layer_end, micro_batch=micro_batch,
                              num_micro=num_micro, device=self.device,
                              global_batch=self.global_batch, optim=self.optim, wgrad=wmode,
-                             stage_index=p.stage, num_stages=pp, dp_shard=shard)
+                             stage_index=p.stage, num_stages=pp, dp_shard=shard, loss=loss)
         if boundary not in ("bf16", "fp8"):
             raise ValueError(f"boundary must be bf16 | fp8, got {boundary!r}")
         self.boundary = boundary if (mesh is not None and pp > 1) else "bf16"
@@ -418,8 +425,11 @@ class Trainer:
         return self.stages[-1] if self.stages[-1].last else None
 
     def set_batch(self, x: Optional[torch.Tensor], labels: Optional[torch.Tensor],
-                  zero_copy: bool = False) -> None:
+                  zero_copy: bool = False, targets: Optional[torch.Tensor] = None) -> None:
         """x: this replica's [rows][Kp] bf16 inputs; labels: [rows] int32 (-1 = padding).
+        Under a dense loss (mse | bce) ``targets`` ([rows][Np] bf16, or [rows][out_dim]) is
+        required on the last stage and ``labels`` is only the row-validity vector (None = every
+        row valid).
 
         ``zero_copy`` (eager mode only): the first stage reads ``x`` in place -- e.g. a row
         slice of an HBM-resident dataset -- instead of copying it into its input buffer."""
@@ -434,7 +444,25 @@ class Trainer:
             else:
                 st.bind_input(st.x_buf)  # never write through an alias of a previous batch
                 st.x_in.copy_(x)
-        if self.last is not None:
+        if self.last is not None and self.last.dense:
+            st = self.last
+            if targets is None:
+                raise ValueError(f"last stage needs dense targets (loss={self.loss_name!r})")
+            if zero_copy and self._graph is None and targets.shape == st.targets_buf.shape and \
+                    targets.dtype == st.targets_buf.dtype and \
+                    targets.device == st.targets_buf.device and \
+                    targets.stride() == st.targets_buf.stride() and \
+                    targets.data_ptr() % 16 == 0:
+                st.bind_targets(targets)
+            else:
+                st.bind_targets(st.targets_buf)
+                st.targets[:, :targets.shape[1]].copy_(targets)
+            if labels is None:
+                st.bind_labels(st.labels_buf)
+                st.labels.zero_()
+        elif targets is not None and self.last is not None:
+            raise ValueError("dense targets need Trainer(loss='mse' | 'bce')")
+        if self.last is not None and not (self.last.dense and labels is None):
             if labels is None:
                 raise ValueError("last stage needs labels")
             st = self.last
@@ -499,6 +527,10 @@ class Trainer:
         # cross-step chain afresh when eager steps resume
         self.executor.xstep_join()
         self.executor._xprimed = False
+        st = self.last
+        if st is not None and st.dense and st.targets.data_ptr() != st.targets_buf.data_ptr():
+            st.targets_buf.copy_(st.targets)  # a graph needs the fixed target buffer: later
+            st.bind_targets(st.targets_buf)   # batches are copied into it
         self._stream = torch.cuda.Stream(self.device)
         self._stream.wait_stream(cur)
         if self.first is not None and self.first.x_in.data_ptr() != self.first.x_buf.data_ptr():
@@ -550,7 +582,10 @@ class Trainer:
         return self.last.loss_sum() / (self.micro_batch * self.num_micro)
 
     def correct(self) -> Optional[int]:
-        return None if self.last is None else int(self.last.correct.sum().item())
+        """Correct predictions of the last step (None under a dense loss: no classes)."""
+        if self.last is None or self.last.dense:
+            return None
+        return int(self.last.correct.sum().item())
 
     def load_weights(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray]) -> None:
         for st in self.stages:

@@ -839,6 +839,73 @@ def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
                           colsum.stride(0) if colsum is not None else 0)
 
 
+DENSE_LOSS_CODE = {"mse": 1, "bce": 2}  # csrc/kernels/dense_loss.hpp DenseLoss
+DENSE_LOSS_ACTS = {"mse": ("linear", "relu", "sigmoid"), "bce": ("sigmoid",)}
+DENSE_COLS_PER_CHUNK = 256  # csrc/kernels/dense_loss.hip DL_COLS
+
+
+def dense_loss_row_blocks(rows: int) -> int:
+    """Row blocks (64 rows, = xent_blocks) of one dense_loss launch over ``rows`` rows."""
+    return xent_blocks(rows)
+
+
+def dense_loss_col_chunks(width: int) -> int:
+    """Column chunks (256 columns) of one dense_loss launch over a padded ``width``."""
+    return -(-width // DENSE_COLS_PER_CHUNK)
+
+
+def check_dense_loss(loss: str, act: str) -> None:
+    """Raise unless ``act`` is an output activation the dense-target ``loss`` is defined for."""
+    if loss not in DENSE_LOSS_ACTS:
+        raise ValueError(f"unknown dense loss {loss!r} (allowed: {sorted(DENSE_LOSS_ACTS)})")
+    if act not in DENSE_LOSS_ACTS[loss]:
+        raise ValueError(f"loss {loss!r} needs a last activation in {DENSE_LOSS_ACTS[loss]}, "
+                         f"got {act!r}")
+
+
+def dense_loss(z, t, dz, n_out, scale, loss, act, row_ok=None, loss_part=None, colsum=None):
+    """Dense-target loss of the output layer from its fp32 pre-activations z and bf16 targets t
+    (first n_out columns; the rest is never read), y = act(z), n = n_out:
+    ``mse``: loss_r = mean_c (y - t)^2, dz = (2 scale / n) (y - t) act'(z);
+    ``bce`` (sigmoid, from the logits): loss_r = mean_c [max(z, 0) - t z + log1p(exp(-|z|))],
+    dz = (scale / n) (sigmoid(z) - t). Rows with row_ok[r] < 0 (row_ok=None: none) are padding:
+    dz = 0, no loss. dz columns n_out..width are written as 0. Per 64-row block rb and
+    256-column chunk ch: loss partial -> loss_part[rb * chunks + ch]; column sums of the stored
+    dz -> colsum[rb][:width] (bias-gradient partials)."""
+    rows, width = dz.shape
+    check_dense_loss(loss, act)
+    nb, nc = dense_loss_row_blocks(rows), dense_loss_col_chunks(width)
+    if rows <= 0 or width % 64 or not 0 < n_out <= width:
+        raise ValueError("dense_loss: dz must be [rows][width], width a multiple of 64 >= n_out")
+    if z.dim() != 2 or t.dim() != 2 or z.shape[0] < rows or t.shape[0] < rows or \
+            z.shape[1] < n_out or t.shape[1] < n_out:
+        raise ValueError("dense_loss: z and t need rows x n_out entries")
+    if loss_part is not None and (loss_part.dtype != torch.float32 or
+                                  loss_part.numel() < nb * nc):
+        raise ValueError("loss_part needs dense_loss_row_blocks * dense_loss_col_chunks fp32 "
+                         "entries")
+    if colsum is not None and (colsum.dtype != torch.float32 or colsum.dim() != 2 or
+                               colsum.shape[0] < nb or colsum.shape[1] < width
+                               or colsum.stride(1) != 1):
+        raise ValueError("colsum must be fp32 [xent_blocks(rows)][>=width]")
+    if row_ok is not None and (row_ok.dtype != torch.int32 or row_ok.numel() < rows or
+                               not row_ok.is_contiguous()):
+        raise ValueError("row_ok must be int32 with one entry per row")
+    if z.dtype != torch.float32 or t.dtype != torch.bfloat16 or dz.dtype != torch.bfloat16:
+        raise ValueError("dense_loss: z fp32, t and dz bf16")
+    if not z.is_cuda:
+        return ref.dense_loss(z, t, dz, n_out, scale, DENSE_LOSS_CODE[loss], ACT_CODE[act],
+                              row_ok, loss_part, colsum, XENT_ROWS_PER_BLOCK,
+                              DENSE_COLS_PER_CHUNK)
+    _rows(z, "z", torch.float32)
+    _rows(t, "t", torch.bfloat16)
+    _rows(dz, "dz", torch.bfloat16)
+    native().dense_loss(_p(z), z.stride(0), _p(t), t.stride(0), _p(row_ok), _p(dz), dz.stride(0),
+                        rows, n_out, width, DENSE_LOSS_CODE[loss], ACT_CODE[act], float(scale),
+                        _p(loss_part), _p(colsum),
+                        colsum.stride(0) if colsum is not None else 0, _stream(z))
+
+
 TAIL_MAX_CLS = 16
 
 

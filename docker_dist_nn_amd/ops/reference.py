@@ -107,6 +107,49 @@ def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
         colsum[:nb, :width] = pad.view(nb, rows_per_block, width).sum(1)
 
 
+def dense_loss(z, t, dz, n_out, scale, loss, act, row_ok=None, loss_part=None, colsum=None,
+               rows_per_block=64, cols_per_chunk=256):
+    """Dense-target losses (loss 1 = mse, 2 = bce on logits) with the kernel's contract and
+    partial layout: fp32 arithmetic per element, dz rounded once to bf16, loss partials per
+    (row block, column chunk), column sums of the stored dz per row block."""
+    rows, width = dz.shape
+    zz = z[:rows, :n_out].float()
+    tt = t[:rows, :n_out].float()
+    valid = torch.ones(rows, dtype=torch.bool) if row_ok is None else row_ok[:rows] >= 0
+    zz = torch.where(valid[:, None], zz, torch.zeros_like(zz))  # padding rows may hold NaN
+    tt = torch.where(valid[:, None], tt, torch.zeros_like(tt))
+    coef = (2.0 if loss == 1 else 1.0) * float(scale) / n_out
+    if loss == 2:
+        y = torch.sigmoid(zz)
+        term = torch.clamp_min(zz, 0.0) - tt * zz + torch.log1p(torch.exp(-zz.abs()))
+        g = coef * (y - tt)
+    else:
+        y = act_fwd(zz, act)
+        d = y - tt
+        term = d * d
+        if act == _SIGMOID:  # y (1 - y) from both tails: sigmoid(z) sigmoid(-z)
+            g = coef * d * (y * torch.sigmoid(-zz))
+        elif act == _RELU:
+            g = torch.where(zz > 0, coef * d, torch.zeros_like(d))
+        else:
+            g = coef * d
+    g = torch.where(valid[:, None], g, torch.zeros_like(g))
+    term = torch.where(valid[:, None], term, torch.zeros_like(term))
+    dz.zero_()
+    dz[:, :n_out] = g.to(dz.dtype)
+    nb = -(-rows // rows_per_block)
+    nc = -(-width // cols_per_chunk)
+    if loss_part is not None:
+        pad = torch.zeros(nb * rows_per_block, nc * cols_per_chunk, dtype=torch.float64)
+        pad[:rows, :n_out] = term.double()
+        part = pad.view(nb, rows_per_block, nc, cols_per_chunk).sum((1, 3)) / n_out
+        loss_part.view(-1)[:nb * nc] = part.reshape(-1).to(loss_part.dtype)
+    if colsum is not None:
+        pad = torch.zeros(nb * rows_per_block, width)
+        pad[:rows] = dz.float()
+        colsum[:nb, :width] = pad.view(nb, rows_per_block, width).sum(1)
+
+
 def softmax_rows(logits, out, n_cls, labels=None, pred=None, correct=None):
     rows = logits.shape[0]
     lg = logits[:rows, :n_cls].float()

@@ -51,7 +51,11 @@ class TensorParallelMLP:
     momentum / weight decay). ``group`` = the TP process group (None = WORLD)."""
 
     def __init__(self, spec: MLPSpec, *, rows: int, tp: int, rank: int, device: torch.device,
-                 group=None, optim: Optional[OptimConfig] = None, seed: int = 0):
+                 group=None, optim: Optional[OptimConfig] = None, seed: int = 0,
+                 loss: str = "softmax_ce"):
+        if loss != "softmax_ce":
+            raise ValueError(f"tensor-parallel training implements loss='softmax_ce' only, got "
+                             f"{loss!r}: the dense losses (mse | bce) run on Trainer")
         if rows % 64:
             raise ValueError("rows must be a multiple of 64 (pad with label -1)")
         self.spec, self.rows, self.tp, self.rank = spec, rows, tp, rank
