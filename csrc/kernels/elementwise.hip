@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "common.hpp"
 #include "elementwise.hpp"
+#include "softmax_wide.hpp"
 
 namespace dnn {
 
@@ -136,7 +137,10 @@ int softmax_xent_blocks(int rows) { return (rows + XENT_ROWS_PER_BLOCK - 1) / XE
 int softmax_xent(const float* logits, long ld_logits, const int* labels, uint16_t* dz, long ld_dz,
                  int rows, int n_cls, int width, float scale, float* loss_part, int* correct,
                  float* colsum, long ld_colsum, hipStream_t stream) {
-  if (rows <= 0 || n_cls <= 0 || n_cls > width || width > 256 || ld_logits < n_cls ||
+  if (width > 256)  // rows that do not fit the registers of a wave: softmax_wide.hip
+    return softmax_xent_wide(logits, ld_logits, labels, dz, ld_dz, rows, n_cls, width, scale,
+                             loss_part, correct, colsum, ld_colsum, stream);
+  if (rows <= 0 || n_cls <= 0 || n_cls > width || ld_logits < n_cls ||
       ld_dz < width || (colsum && ld_colsum < width))
     return -1;
   const dim3 grid(softmax_xent_blocks(rows)), block(256);
@@ -204,7 +208,10 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 
 int softmax_rows(const float* logits, long ld_in, float* out, long ld_out, int rows, int n_cls,
                  const int* labels, int* pred, int* correct, hipStream_t stream) {
-  if (rows <= 0 || n_cls <= 0 || n_cls > 256 || ld_in < n_cls || (out && ld_out < n_cls))
+  if (n_cls > 256)
+    return softmax_rows_wide(logits, ld_in, out, ld_out, rows, n_cls, labels, pred, correct,
+                             stream);
+  if (rows <= 0 || n_cls <= 0 || ld_in < n_cls || (out && ld_out < n_cls))
     return -1;
   const dim3 grid((rows + 3) / 4), block(256);
   if (n_cls <= 64)

@@ -815,8 +815,17 @@ def xent_blocks(rows: int) -> int:
 def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None, colsum=None):
     """dz = (softmax - onehot) * scale; per 64-row block: loss partial sum -> loss_part,
     #argmax==label -> correct (int32), and (optional) dz column sums -> colsum
-    [xent_blocks(rows)][width] (bias-gradient partials)."""
+    [xent_blocks(rows)][width] (bias-gradient partials).
+
+    ``width`` = dz.shape[1] >= n_cls is any size: up to 256 columns a wave holds the row in
+    registers (csrc/kernels/elementwise.hip), wider rows are swept (csrc/kernels/
+    softmax_wide.hip) -- one contract, chosen inside the native launcher. Columns n_cls..width
+    of dz are written as zeros; logits there, and in rows with a label < 0, are never used."""
     rows, width = dz.shape
+    if rows <= 0 or not 0 < n_cls <= width:
+        raise ValueError("softmax_xent: dz must be [rows][width] with 0 < n_cls <= width")
+    if logits.dim() != 2 or logits.shape[0] < rows or logits.shape[1] < n_cls:
+        raise ValueError("softmax_xent: logits need rows x n_cls entries")
     if loss_part is not None and loss_part.numel() < xent_blocks(rows):
         raise ValueError("loss_part needs xent_blocks(rows) entries")
     if correct is not None and (correct.dtype != torch.int32 or
@@ -963,12 +972,23 @@ def mlp_tail(x, w3, b3, w4, b4, labels, h3, dz4, dz3, dz2, n_cls, scale, act3="r
 
 
 def softmax_rows(logits, out, n_cls, labels=None, pred=None, correct=None):
+    """Inference softmax of the first n_cls columns (any n_cls; above 256 the sweeping kernel of
+    csrc/kernels/softmax_wide.hip): probabilities -> out (optional, may be ``logits`` itself;
+    nothing is written beyond column n_cls), argmax (lowest index on ties) -> pred (int32), and
+    #argmax==label ADDED to correct[0] (int32)."""
     rows = logits.shape[0]
+    if logits.dim() != 2 or rows <= 0 or not 0 < n_cls <= logits.shape[1]:
+        raise ValueError("softmax_rows: logits must be [rows][>=n_cls], n_cls > 0")
+    if out is not None and (out.dim() != 2 or out.shape[0] < rows or out.shape[1] < n_cls):
+        raise ValueError("softmax_rows: out needs rows x n_cls entries")
     if not logits.is_cuda:
         return ref.softmax_rows(logits, out, n_cls, labels, pred, correct)
     _rows(logits, "logits", torch.float32)
     if out is not None:
         _rows(out, "out", torch.float32)
+    for t, name, n in ((labels, "labels", rows), (pred, "pred", rows), (correct, "correct", 1)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < n):
+            raise ValueError(f"softmax_rows: {name} must be int32 with at least {n} entries")
     native().softmax_rows(_p(logits), logits.stride(0), _p(out),
                           out.stride(0) if out is not None else 0, rows, n_cls, _p(labels),
                           _p(pred), _p(correct), _stream(logits))

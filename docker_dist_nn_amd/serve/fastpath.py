@@ -29,7 +29,11 @@ header read and a host send per hop. Here:
   wrote, and serves request after request with no host work at all -- no announcement read, no
   launch; the host thread only relaunches it after an idle exit and publishes its progress
   counter (coherent host memory) for rank 0's blame. A stage that must use the GPU for
-  something else (a message-chain request) pauses it first (``paused``);
+  something else (a message-chain request) pauses it first (``paused``). Its softmax keeps a
+  request's fp32 logits in LDS (``_persist_ok``: rows + logits within 64 KiB), so a wide
+  softmax stage -- 1000 classes at 16 or more rows per request, say -- is refused there and
+  served by the host-driven loop through ``InferenceStage.forward``, whose row softmax has no
+  class limit (csrc/kernels/softmax_wide.hip beyond 256);
 * larger requests and any set-up that cannot map its peers keep using the message-passing
   chain (serve/chain.py), which stays the fallback.
 """
