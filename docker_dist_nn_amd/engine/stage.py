@@ -15,10 +15,9 @@ This is the MI355X replacement of the reference's stage worker
 
 Per layer the compute is three fused gfx950 kernels: forward GEMM with bias+activation
 epilogue, dgrad GEMM whose epilogue applies the previous layer's activation derivative (read
-from the stored activation -- no mask tensor), and the wgrad GEMM. The last layer of the last
-stage writes fp32 logits and runs the fused softmax-cross-entropy kernel -- or, with
-``loss="mse" | "bce"``, fp32 pre-activations and the dense-target loss kernel (ops.dense_loss)
-against a bf16 target matrix.
+from the stored activation -- no mask tensor), and the wgrad GEMM. How the last stage ends --
+which kernels run its last layer(s) and the loss, and which dgrads they absorb -- is its loss
+head's business (engine/loss_head.py); a Stage only asks the head which layers it covers.
 """
 from __future__ import annotations
 
@@ -34,6 +33,7 @@ from .. import ops
 from ..models.mlp import LayerGeom, MLPSpec, round_up
 from ..utils.native import native
 from .. import switches
+from .loss_head import LossHead, check_loss
 
 _ALIGN = 64  # elements; keeps every layer's region 256-B aligned
 RELU_MASK_AUTO_WIDTH = 1024  # DNN_RELU_MASK=auto: masks for hidden layers at least this wide
@@ -391,6 +391,19 @@ class StageParams:
         self.refresh_t(step=True)
 
 
+def _of_head(path: str, default=None) -> property:
+    """Read-only ``stage.head.<path>``; ``default`` where the stage has no head (it is not the
+    last) or the head has no such part (targets of a class-label loss)."""
+    def get(self):
+        obj = self.head
+        for name in path.split("."):
+            if obj is None:
+                return default
+            obj = getattr(obj, name)
+        return obj
+    return property(get)
+
+
 class Stage:
     """Compute of one pipeline stage for one step (see module doc)."""
 
@@ -402,9 +415,8 @@ class Stage:
         if not 0 <= layer_start < layer_end <= len(spec.layers):
             raise ValueError("bad layer range")
         # loss of the last stage: softmax cross-entropy against int32 class labels (default),
-        # or a dense-target loss (ops.dense_loss: mse | bce) against a bf16 target matrix
-        if loss != "softmax_ce":
-            ops.check_dense_loss(loss, spec.layers[-1].activation)
+        # or a dense-target loss (mse | bce) against a bf16 target matrix
+        check_loss(loss, spec.layers[-1].activation)
         self.loss = loss
         if micro_batch <= 0 or micro_batch % 64:
             raise ValueError("micro_batch must be a positive multiple of 64 (MFMA row tiles); "
@@ -435,20 +447,20 @@ class Stage:
         g0 = self.geoms[0]
         self.x_buf = torch.zeros(R, g0.kp, dtype=bf, device=dev)
         self.x_in = self.x_buf  # may be re-pointed at a resident dataset slice (zero-copy)
-        # the last layer's softmax-CE is fused into its GEMM epilogue when the padded class
-        # count is one 64/128-wide tile: logits then never exist in memory
-        gl = self.geoms[-1]
-        self.dense = self.last and self.loss != "softmax_ce"
-        self.fused_xent = (self.last and not self.dense and gl.np_ in (64, 128) and
-                           switches.get("DNN_FUSED_XENT") == "1")
+        # The loss head (last stage only) runs the forward of local layers >= fwd_from and the
+        # dgrads of local layers >= dgrad_from inside its own kernels; everything below those
+        # two indices is a GEMM of this stage (both are L without a head)
+        L = len(self.geoms)
+        self.head = head = LossHead.choose(self)
+        self.fwd_from = head.fwd_from if head else L
+        self.dgrad_from = head.dgrad_from if head else L
         self.acts: list[torch.Tensor] = []  # output of local layer i
         for i, g in enumerate(self.geoms):
-            is_logits = self.last and i == len(self.geoms) - 1
-            if is_logits and self.fused_xent:
-                self.acts.append(torch.empty(0, g.np_, dtype=f32, device=dev))
-            else:
-                self.acts.append(torch.zeros(R, g.np_, dtype=f32 if is_logits else bf,
+            if head and i == L - 1:  # fp32, or never in memory at all
+                self.acts.append(torch.zeros(R if head.logits else 0, g.np_, dtype=f32,
                                              device=dev))
+            else:
+                self.acts.append(torch.zeros(R, g.np_, dtype=bf, device=dev))
         # 1-bit ReLU masks of the hidden outputs consumed by this stage's own dgrads (GPU,
         # DNN_RELU_MASK=1; off by default: measured 0.380 vs 0.371 ms on the headline step,
         # the byte-granular mask stores/loads cost more than the activation bytes saved):
@@ -456,9 +468,7 @@ class Stage:
         # activation itself is still kept: it is the next layer's wgrad operand)
         # DNN_RELU_MASK=2: fragment-order masks (ops.FragMask: one 16-byte access per lane), only
         # where a GEMM dgrad of this stage consumes them and it runs the forward's tile shape
-        self.tail = self._tail_ok()
         mask_mode = switches.get("DNN_RELU_MASK") if dev.type == "cuda" else "0"
-        L = len(self.geoms)
         self.relu_mask = []
         for i, g in enumerate(self.geoms):
             m = None
@@ -469,23 +479,13 @@ class Stage:
                 else mask_mode
             if mode_i == "1" and i < L - 1 and g.spec.activation == "relu":
                 m = torch.zeros(R, g.np_ // 8, dtype=torch.uint8, device=dev)
-            elif mode_i == "2" and i < L - 1 and g.spec.activation == "relu" and \
-                    not (self.tail and i + 1 >= L - 2):
+            elif mode_i == "2" and i + 1 < self.dgrad_from and g.spec.activation == "relu":
                 tiles = ops.frag_mask_tiles(self.mb, g.np_, g.kp, self.geoms[i + 1].np_)
                 if tiles is not None:
                     m = ops.FragMask.alloc(R, g.np_, tiles, dev)
             self.relu_mask.append(m)
         self.dz = [torch.zeros(R, g.np_, dtype=bf, device=dev) for g in self.geoms]
         self.dx_send = None if self.first else torch.zeros(R, g0.kp, dtype=bf, device=dev)
-        self.labels = torch.full((R,), -1, dtype=torch.int32, device=dev) if self.last else None
-        self.labels_buf = self.labels  # owned buffer; ``labels`` may alias a dataset slice
-        # dense-target loss: bf16 targets [rows][Np] (``labels`` is then only the row-validity
-        # vector, -1 = padding row)
-        self.targets = torch.zeros(R, gl.np_, dtype=bf, device=dev) if self.dense else None
-        self.targets_buf = self.targets  # owned buffer; ``targets`` may alias a dataset slice
-        # Narrow classifier tail (csrc/kernels/mlp_tail.hip): the forward of the last two
-        # layers, the softmax CE and both of their dgrads run as ONE kernel inside the last
-        # layer's forward; the second-to-last layer's forward and both dgrads are then no-ops.
         # K-major weight gradients (ops.linear_wgrad dzt / xt): for big hidden layers whose dZ
         # and input activation come from this stage's own one-tile GEMMs, those GEMMs also write
         # the transposed copies in their epilogues (+1 write of each, -20 % wgrad time)
@@ -493,33 +493,19 @@ class Stage:
         self.actT: dict[int, torch.Tensor] = {}
         kk = switches.get("DNN_WGRAD_KK")
         if dev.type == "cuda" and self.wgrad_mode == "batched" and kk != "0":
-            L = len(self.geoms)
             for i in range(1, L):
                 g = self.geoms[i]
                 big = kk == "1" or g.np_ * g.kp >= (1 << 24)
-                dz_by_dgrad = i + 1 < L and not (self.tail and i + 1 >= L - 2) and \
-                    self.relu_mask[i] is None
-                x_by_fwd = not (self.tail and i - 1 >= L - 2) and self.relu_mask[i - 1] is None
+                dz_by_dgrad = i + 1 < self.dgrad_from and self.relu_mask[i] is None
+                x_by_fwd = i - 1 < self.fwd_from and self.relu_mask[i - 1] is None
                 if big and dz_by_dgrad and x_by_fwd:
                     self.dzT[i] = torch.zeros(g.np_, R, dtype=bf, device=dev)
                     self.actT[i - 1] = torch.zeros(g.kp, R, dtype=bf, device=dev)
         # dgrad GEMMs read W^T (contraction-contiguous B operand, see ops.linear_dgrad)
         if dev.type == "cuda" and switches.get("DNN_DGRAD_WT") == "1":
-            L = len(self.geoms)
-            for i in range(L):
-                if (i > 0 or not self.first) and not (self.tail and i >= L - 2):
+            for i in range(self.dgrad_from):
+                if i > 0 or not self.first:
                     self.params.enable_wt(i)
-        if self.tail:
-            self.xent_per_micro = ops.tail_blocks(self.mb)
-        else:
-            self.xent_per_micro = (self.mb // ops.xent_tiles(self.mb, gl.np_)[0]
-                                   if self.fused_xent else ops.xent_blocks(self.mb))
-        # loss partials per micro-batch: one per row block, times the dense loss's column chunks
-        self.loss_chunks = ops.dense_loss_col_chunks(gl.np_) if self.dense else 1
-        self.loss_part = torch.zeros(self.xent_per_micro * self.loss_chunks * self.nm, dtype=f32,
-                                     device=dev)
-        # per-block correct counts, written (not accumulated) by the loss kernels
-        self.correct = torch.zeros(self.xent_per_micro * self.nm, dtype=torch.int32, device=dev)
         # wgrad geometry: batched = one GEMM over all rows; per_micro = one per micro-batch
         wrows = R if self.wgrad_mode == "batched" else self.mb
         if self.wgrad_algo == "streamk":  # balanced stream-K, reduced straight into the grads
@@ -533,23 +519,19 @@ class Stage:
                           for s, g in zip(self.w_splits, self.geoms)]
         # Bias-gradient partials (column sums of dZ) come fused from whichever kernel produces
         # dZ: the dgrad epilogue of the next local layer (one partial per output row tile), the
-        # softmax-CE kernel (one per 64-row block), or -- for a gradient received from the next
-        # stage -- a colsum kernel. self.bp[i] = partials per micro-batch.
+        # loss head (one per row block of its kernel), or -- for a gradient received from the
+        # next stage -- a colsum kernel. self.bp[i] = partials per micro-batch.
         self.bp = []
-        L = len(self.geoms)
         for i in range(L):
-            if i < L - 1:
+            if head and i >= self.dgrad_from - 1:
+                self.bp.append(head.blocks)
+            elif i < L - 1:
                 g1 = self.geoms[i + 1]
                 self.bp.append(self.mb // ops.dgrad_tiles(self.mb, g1.kp, g1.np_)[0])
-            elif self.last:
-                self.bp.append(self.xent_per_micro)
             else:
                 # one partial per 128 rows: enough workgroups to fill the chip (1024-row
                 # partitions left a 4096-row boundary colsum at 32 workgroups, 12 us)
                 self.bp.append(max(1, self.mb // 128))
-        if self.tail:  # dz of the last three local layers come from the tail kernel
-            for i in range(L - 3, L):
-                self.bp[i] = self.xent_per_micro
         self.bpart = [torch.zeros(self.bp[i] * self.nm, g.np_, dtype=f32, device=dev)
                       for i, g in enumerate(self.geoms)]
         self._w_done = 0
@@ -560,19 +542,20 @@ class Stage:
         self._recording = False
         self._has_w = False
         self._o_native = False  # "O" recorded (device-side lr / step)
-        self._rx = self._rl = self._rt = None
+        self._rx = None
         self.boundary = "bf16"
         self._fp8_next = self._fp8_prev = False
 
-    def _tail_ok(self) -> bool:
-        if not (self.fused_xent and self.device.type == "cuda" and len(self.geoms) >= 3 and
-                switches.get("DNN_TAIL") == "1"):
-            return False
-        g2, g3, g4 = self.geoms[-3], self.geoms[-2], self.geoms[-1]
-        acts = ("relu", "sigmoid", "linear")
-        return (ops.tail_supported(g3.kp, g3.np_, g4.np_, self.n_cls) and
-                g3.spec.activation in acts and g2.spec.activation in acts and
-                self.mb % 16 == 0)
+    # the head's choice and buffers, readable where the stage's own used to be
+    tail = _of_head("tail", False)
+    fused_xent = _of_head("fused_xent", False)
+    dense = _of_head("dense", False)
+    loss_part = _of_head("loss_part")
+    correct = _of_head("correct")
+    labels = _of_head("labels.cur")
+    labels_buf = _of_head("labels.buf")
+    targets = _of_head("targets.cur")
+    targets_buf = _of_head("targets.buf")
 
     # ---- fp8 pipeline boundary (opt-in: Trainer(boundary="fp8")) -------------------------
     def enable_fp8_boundary(self, has_prev: bool, has_next: bool) -> None:
@@ -658,53 +641,17 @@ class Stage:
             self._forward_layer(j, i)
 
     def _forward_layer(self, j: int, i: int) -> None:
+        if i >= self.fwd_from:
+            # the head's layers: all of its work is launched at (and recorded under) the last
+            if i == len(self.geoms) - 1:
+                self.head.forward(self, j)
+            return
         r = self.rows_of(j)
         p = self.params
-        g = self.geoms[i]
-        x = self.input_of(i)[r]
-        y = self.acts[i][r]
-        L = len(self.geoms)
-        if self.tail and i == L - 2:
-            return  # computed by the tail kernel at i == L - 1
-        if self.tail and i == L - 1:
-            k = j * self.xent_per_micro
-            ops.mlp_tail(self.acts[L - 3][r], p.wbf(L - 2), p.b32(L - 2), p.wbf(L - 1),
-                         p.b32(L - 1), self.labels[r], self.acts[L - 2][r], self.dz[L - 1][r],
-                         self.dz[L - 2][r], self.dz[L - 3][r], self.n_cls,
-                         1.0 / self.global_batch, act3=self.geoms[L - 2].spec.activation,
-                         act2=self.geoms[L - 3].spec.activation,
-                         loss_part=self.loss_part[k:k + self.xent_per_micro],
-                         correct=self.correct[k:k + self.xent_per_micro],
-                         cs4=self._bpart(L - 1, j), cs3=self._bpart(L - 2, j),
-                         cs2=self._bpart(L - 3, j))
-        elif self.last and i == len(self.geoms) - 1 and self.fused_xent:
-            k = j * self.xent_per_micro
-            ops.linear_fwd_xent(x, p.wbf(i), p.b32(i), self.dz[i][r], self.labels[r],
-                                self.n_cls, 1.0 / self.global_batch,
-                                self.loss_part[k:k + self.xent_per_micro],
-                                self.correct[k:k + self.xent_per_micro],
-                                colsum=self._bpart(i, j))
-        elif self.dense and i == len(self.geoms) - 1:
-            ops.linear_fwd(x, p.wbf(i), p.b32(i), y, act="linear")  # fp32 pre-activations
-            k = j * self.xent_per_micro * self.loss_chunks
-            ops.dense_loss(y, self.targets[r], self.dz[i][r], self.n_cls,
-                           1.0 / self.global_batch, self.loss, g.spec.activation,
-                           row_ok=self.labels[r],
-                           loss_part=self.loss_part[k:k + self.xent_per_micro * self.loss_chunks],
-                           colsum=self._bpart(i, j))
-        elif self.last and i == len(self.geoms) - 1:
-            ops.linear_fwd(x, p.wbf(i), p.b32(i), y, act="linear")  # fp32 logits
-            k = j * self.xent_per_micro
-            ops.softmax_xent(y, self.labels[r], self.dz[i][r], self.n_cls,
-                             1.0 / self.global_batch,
-                             self.loss_part[k:k + self.xent_per_micro],
-                             self.correct[k:k + self.xent_per_micro],
-                             colsum=self._bpart(i, j))
-        else:
-            m = self.relu_mask[i]
-            ops.linear_fwd(x, p.wbf(i), p.b32(i), y, act=g.spec.activation,
-                           mask=None if m is None else m[r],
-                           yt=self.actT[i][:, r] if i in self.actT else None)
+        m = self.relu_mask[i]
+        ops.linear_fwd(self.input_of(i)[r], p.wbf(i), p.b32(i), self.acts[i][r],
+                       act=self.geoms[i].spec.activation, mask=None if m is None else m[r],
+                       yt=self.actT[i][:, r] if i in self.actT else None)
 
     def backward(self, j: int) -> None:
         """dgrad chain of micro-batch j; dZ of the last local layer must already be present."""
@@ -722,8 +669,8 @@ class Stage:
     def _backward_layer(self, j: int, i: int) -> None:
         """dgrad of local layer i for micro-batch j: dZ of layer i -> dZ of layer i-1 (or the
         gradient sent to the previous stage when i == 0)."""
-        if self.tail and i >= len(self.geoms) - 2:
-            return  # both dgrads ran inside the tail kernel (forward of micro-batch j)
+        if i >= self.dgrad_from:
+            return  # ran inside the loss head's kernel (forward of micro-batch j)
         r = self.rows_of(j)
         p = self.params
         if i > 0:
@@ -1003,16 +950,10 @@ class Stage:
         nat = native()
         prog = nat.Program()
         self.x_in = self.x_buf
-        if self.labels is not None:
-            self.labels = self.labels_buf
         self._rx = (prog.region(self.x_buf.data_ptr(), self.x_buf.numel() * 2)
                     if self.first else None)
-        self._rl = (prog.region(self.labels_buf.data_ptr(), self.labels_buf.numel() * 4)
-                    if self.labels is not None else None)
-        if self.targets is not None:
-            self.targets = self.targets_buf
-        self._rt = (prog.region(self.targets_buf.data_ptr(), self.targets_buf.numel() * 2)
-                    if self.targets is not None else None)
+        for slot in (self.head.slots() if self.head else ()):
+            slot.attach(prog)
         # DNN_H0_DOUBLE: the layer-0 activation alternates between two buffers from step to
         # step (a relocatable region re-based by flip_h0), so the next step's layer-0 forward
         # never has to wait for this step's side-stream weight gradient that reads it
@@ -1020,8 +961,7 @@ class Stage:
         L = len(self.geoms)
         self.h0_double = (switches.get("DNN_H0_DOUBLE") == "1" and self.device.type == "cuda"
                           and self.first and self.last and self.nm == 1 and L >= 2 and
-                          0 not in self.actT and
-                          not (self.tail and L - 2 <= 0))
+                          0 not in self.actT and 0 < self.fwd_from)
         self._rh0 = None
         if self.h0_double:
             a0 = self.acts[0]
@@ -1130,37 +1070,31 @@ class Stage:
             self._prog.rebase(self._rx, x.data_ptr())
 
     def bind_labels(self, y: torch.Tensor) -> None:
-        self.labels = y
-        if self._prog is not None and self._rl is not None:
-            self._prog.rebase(self._rl, y.data_ptr())
+        self.head.labels.bind(y)
 
     def bind_targets(self, t: torch.Tensor) -> None:
         """Dense loss: the last stage reads the bf16 targets ``t`` ([rows][Np], the row stride
         of ``targets_buf``) in place from now on."""
-        self.targets = t
-        if self._prog is not None and self._rt is not None:
-            self._prog.rebase(self._rt, t.data_ptr())
+        self.head.targets.bind(t)
+
+    def pin_input(self) -> None:
+        """Before a graph capture: a graph needs the fixed input buffer (later batches are
+        copied into it), so an input bound in place moves there."""
+        if self.x_in.data_ptr() != self.x_buf.data_ptr():
+            self.x_buf.copy_(self.x_in)
+            self.bind_input(self.x_buf)
 
     # convenience: a whole step when this stage holds the entire model ----------------------
     def set_batch(self, x: torch.Tensor, labels: Optional[torch.Tensor],
                   targets: Optional[torch.Tensor] = None) -> None:
         self.bind_input(self.x_buf)  # never write through an alias of the caller's dataset
         self.x_in.copy_(x)
-        if self.labels is not None:
-            self.bind_labels(self.labels_buf)
-            if labels is None and self.dense:
-                self.labels.zero_()  # every row valid
-            else:
-                self.labels.copy_(labels)
-        if self.dense:
-            if targets is None:
-                raise ValueError(f"loss {self.loss!r} needs dense targets")
-            self.bind_targets(self.targets_buf)
-            self.targets[:, :targets.shape[1]].copy_(targets)
+        if self.head is not None:
+            self.head.set_batch(labels, targets)
 
     def loss_sum(self) -> float:
         """Sum of per-row losses of the last step (fixed-order fp64 host sum)."""
-        return float(self.loss_part.detach().cpu().double().sum())
+        return self.head.loss_sum()
 
     def flops_per_step(self) -> float:
         f = 0.0

@@ -30,6 +30,7 @@ from ..parallel.groups import Mesh
 from ..parallel.pipeline import GradSync, PipelineExecutor
 from ..partition import balanced_distribution, plan_stages
 from ..utils.native import native
+from .loss_head import check_loss
 from .stage import OptimConfig, Stage
 from .. import switches
 
@@ -73,10 +74,7 @@ class Trainer:
                  dp_reduce: str = "allreduce", loss: str = "softmax_ce"):
         # loss: "softmax_ce" (int32 class labels) or a dense-target loss against a bf16 target
         # matrix -- "mse" (last activation linear | relu | sigmoid) or "bce" (sigmoid)
-        if loss != "softmax_ce":
-            from .. import ops
-
-            ops.check_dense_loss(loss, spec.layers[-1].activation)
+        check_loss(loss, spec.layers[-1].activation)
         self.loss_name = loss
         self.spec = spec
         self.mesh = mesh
@@ -444,35 +442,8 @@ class Trainer:
             else:
                 st.bind_input(st.x_buf)  # never write through an alias of a previous batch
                 st.x_in.copy_(x)
-        if self.last is not None and self.last.dense:
-            st = self.last
-            if targets is None:
-                raise ValueError(f"last stage needs dense targets (loss={self.loss_name!r})")
-            if zero_copy and self._graph is None and targets.shape == st.targets_buf.shape and \
-                    targets.dtype == st.targets_buf.dtype and \
-                    targets.device == st.targets_buf.device and \
-                    targets.stride() == st.targets_buf.stride() and \
-                    targets.data_ptr() % 16 == 0:
-                st.bind_targets(targets)
-            else:
-                st.bind_targets(st.targets_buf)
-                st.targets[:, :targets.shape[1]].copy_(targets)
-            if labels is None:
-                st.bind_labels(st.labels_buf)
-                st.labels.zero_()
-        elif targets is not None and self.last is not None:
-            raise ValueError("dense targets need Trainer(loss='mse' | 'bce')")
-        if self.last is not None and not (self.last.dense and labels is None):
-            if labels is None:
-                raise ValueError("last stage needs labels")
-            st = self.last
-            if zero_copy and self._graph is None and labels.shape == st.labels_buf.shape and \
-                    labels.dtype == st.labels_buf.dtype and \
-                    labels.device == st.labels_buf.device and labels.is_contiguous():
-                st.bind_labels(labels)
-            else:
-                st.bind_labels(st.labels_buf)
-                st.labels.copy_(labels)
+        if self.last is not None:
+            self.last.head.set_batch(labels, targets, zero_copy and self._graph is None)
 
     def step(self) -> None:
         if self._graph is not None:
@@ -527,14 +498,14 @@ class Trainer:
         # cross-step chain afresh when eager steps resume
         self.executor.xstep_join()
         self.executor._xprimed = False
-        st = self.last
-        if st is not None and st.dense and st.targets.data_ptr() != st.targets_buf.data_ptr():
-            st.targets_buf.copy_(st.targets)  # a graph needs the fixed target buffer: later
-            st.bind_targets(st.targets_buf)   # batches are copied into it
+        # a graph needs fixed batch buffers (later batches are copied into them): whatever a
+        # zero-copy set_batch bound in place moves into the stages' own
+        if self.first is not None:
+            self.first.pin_input()
+        if self.last is not None:
+            self.last.head.pin()
         self._stream = torch.cuda.Stream(self.device)
         self._stream.wait_stream(cur)
-        if self.first is not None and self.first.x_in.data_ptr() != self.first.x_buf.data_ptr():
-            self.first.x_in = self.first.x_buf  # a graph needs the fixed input buffer
         graphs = []
         self.executor.capturing = True  # single-stream plan: the graph serialises anyway
         with torch.cuda.stream(self._stream):
@@ -583,9 +554,7 @@ class Trainer:
 
     def correct(self) -> Optional[int]:
         """Correct predictions of the last step (None under a dense loss: no classes)."""
-        if self.last is None or self.last.dense:
-            return None
-        return int(self.last.correct.sum().item())
+        return None if self.last is None else self.last.head.correct_sum()
 
     def load_weights(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray]) -> None:
         for st in self.stages:

@@ -61,8 +61,8 @@ def test_gpu_wide_output_trains(dev):
     """320 padded output columns: more than the 256 the stand-alone cross-entropy kernel takes."""
     tr, losses = _run(WIDE, "mse", dev, 6, lr=5.0)
     st = tr.last
-    assert st.dz[-1].shape[1] == 320 and st.loss_chunks == 2
-    assert st.loss_part.numel() == st.xent_per_micro * 2 * NM
+    assert st.dz[-1].shape[1] == 320 and st.head.chunks == 2
+    assert st.loss_part.numel() == st.head.blocks * 2 * NM
     assert all(np.isfinite(losses)) and losses[-1] < losses[0]
 
 

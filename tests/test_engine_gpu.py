@@ -71,6 +71,28 @@ def test_gpu_graph_replay_equals_eager(dev):
         assert np.array_equal(wa[k][0], wb[k][0])
 
 
+def test_gpu_capture_pins_zero_copy_batch(dev):
+    """A capture after a zero-copy set_batch moves inputs and labels into the trainer's own
+    buffers, which later (copying) set_batch calls fill: the replay reads the NEW batch, exactly
+    as after a copying first set_batch."""
+    spec = MLPSpec.parse("784-512-256-128-10")
+    b0, b1 = _batch(1024, dev, seed=1), _batch(1024, dev, seed=2)
+    out = []
+    for zero_copy in (True, False):
+        tr = Trainer(spec, device=dev, micro_batch=1024, optim=OptimConfig(lr=0.1))
+        tr.set_batch(*b0, zero_copy=zero_copy)
+        tr.capture(warmup=0)  # capture executes one real step
+        losses = [tr.loss()]
+        tr.set_batch(*b1)
+        tr.step()
+        losses.append(tr.loss())
+        out.append((losses, tr.local_weights()))
+    (la, wa), (lb, wb) = out
+    assert la == lb
+    for k in wa:
+        assert np.array_equal(wa[k][0], wb[k][0]) and np.array_equal(wa[k][1], wb[k][1])
+
+
 def test_gpu_bitwise_deterministic(dev):
     spec = MLPSpec.parse("784-512-256-128-10")
     _, la = _run(spec, dev, 3, micro_batch=2048)
