@@ -599,6 +599,7 @@ PYBIND11_MODULE(_native, m) {
               },
               stream);
         });
+  m.def("fp8_tiny_amax", []() { return dnn::FP8_TINY_AMAX; });
   m.def("quant_rows_fp8", [](uintptr_t x, long ldx, int rows, int cols, uintptr_t q, long ldq,
                              uintptr_t scale, uintptr_t stream) {
     launch(

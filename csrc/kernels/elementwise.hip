@@ -734,6 +734,16 @@ int transpose_bf16(const uint16_t* src, long ld_src, int rows, int cols, uint16_
 // fp8 pipeline boundary (opt-in): a row of a bf16 activation / gradient is sent as OCP e4m3
 // bytes plus one fp32 scale (row amax / 448), halving the bytes on the xGMI hop. One wave per
 // row; 8 elements (one 16-byte bf16 load, one 8-byte fp8 store) per lane per iteration.
+//
+// The format, exactly (tests/_fp8_oracle.py is its reference): amax = max |x| of the row,
+// scale = fl32(amax / 448), inv = fl32(448 / amax) -- both IEEE-rounded fp32 quotients (hipcc's
+// default; the build passes no fast-math flag, and tests/test_fp8_boundary_gpu.py compares the
+// codes bit for bit, so an approximate reciprocal fails there) -- and the code of x is
+// e4m3(fl32(x * inv)), round to nearest, ties to even. A row with amax < FP8_TINY_AMAX (2^-110)
+// is sent as a zero row (scale = inv = 0, codes +-0): 448 / amax would overflow to inf below
+// 448 / FLT_MAX ~ 1.3e-36, turning the whole row into NaN, and what is dropped is below 2^-110
+// absolute. Dequantisation is bf16(fl32(e4m3(code) * scale)). A NaN or +-inf element comes back
+// non-finite at its position; the rest of such a row is not specified.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_amax(float v) {
 #pragma unroll
@@ -757,7 +767,8 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const u16* __restri
     for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(bf2f(e[k])));
   }
   amax = wave_amax(amax);
-  const float s = amax / 448.f, inv = amax > 0.f ? 448.f / amax : 0.f;
+  const bool send = amax >= FP8_TINY_AMAX;  // false for a zero row too
+  const float s = send ? amax / 448.f : 0.f, inv = send ? 448.f / amax : 0.f;
   if (lane == 0) scale[row] = s;
   unsigned char* qr = q + (long)row * ldq;
   for (int c = lane * 8; c < cols; c += 512) {

@@ -101,6 +101,9 @@ int transpose_bf16(const uint16_t* src, long ld_src, int rows, int cols, uint16_
                    long ld_dst, hipStream_t stream);
 
 // fp8 (OCP e4m3) pipeline boundary: row-wise amax scaling; q [rows][ldq] bytes, scale [rows].
+// A row whose amax is below FP8_TINY_AMAX is sent as a zero row (scale 0, codes +-0); the same
+// constant is ops.FP8_TINY_AMAX of the CPU path.
+constexpr float FP8_TINY_AMAX = 0x1p-110f;
 int quant_rows_fp8(const uint16_t* x, long ldx, int rows, int cols, unsigned char* q, long ldq,
                    float* scale, hipStream_t stream);
 int dequant_rows_fp8(const unsigned char* q, long ldq, const float* scale, int rows, int cols,

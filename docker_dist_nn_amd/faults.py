@@ -6,8 +6,9 @@ ignored (/root/reference/src/run_grpc_fcnn.py:319). Here:
 
 * :class:`Watchdog` -- a per-rank thread; the training/serving loop calls ``beat()`` every
   step. If no beat arrives within ``timeout`` seconds (a hung collective, a wedged kernel, a
-  peer that died mid-send) it logs which phase stalled, dumps every thread's stack and exits
-  the process with ``EXIT_WATCHDOG`` so the launcher's fail-fast monitor tears the job down.
+  peer that died mid-send) it logs which phase stalled, dumps every thread's stack and, two polls
+  later (time for the other stalled ranks to report too), exits the process with
+  ``EXIT_WATCHDOG`` so the launcher's fail-fast monitor tears the job down.
   (RCCL's own async error handling + the process-group timeout cover the comm side as well.)
 * :class:`FaultInjector` -- ``DNN_FAULT="stage:1,step:3,kind:crash|hang|nan|raise"`` makes the
   matching rank fail at that step, for tests of the detection paths.
@@ -58,7 +59,8 @@ class Watchdog:
         self._stop.set()
 
     def _run(self) -> None:
-        while not self._stop.wait(min(1.0, self.timeout / 4)):
+        poll = min(1.0, self.timeout / 4)
+        while not self._stop.wait(poll):
             idle = time.monotonic() - self._last
             if idle > self.timeout:
                 self.fired = True
@@ -71,6 +73,11 @@ class Watchdog:
                 if self.on_fire is not None:
                     self.on_fire(self)
                 if self.exit_on_fire:
+                    # ranks that wait for a hung peer stall with it and fire within one poll of
+                    # each other; leave the others two polls to report their own phase before
+                    # this exit makes the launcher tear the job down (else the log may name
+                    # only a waiting rank, never the hung one)
+                    time.sleep(2 * poll)
                     os._exit(EXIT_WATCHDOG)
                 return
 

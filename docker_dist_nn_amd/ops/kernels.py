@@ -606,18 +606,30 @@ def transpose_multi(pairs):
 FP8_MAX = 448.0  # OCP e4m3 (gfx950's fp8; not the fnuz variant of MI300)
 
 
+FP8_TINY_AMAX = 2.0 ** -110  # rows below it are sent as zeros (csrc/kernels/elementwise.hpp)
+
+
 def quant_rows_fp8(x, q, scale):
-    """Pipeline-boundary compression: q[r] = e4m3(x[r] / scale[r]), scale[r] = amax(x[r])/448.
-    x bf16 [rows][cols], q uint8 [rows][>=cols], scale fp32 [rows]."""
+    """Pipeline-boundary compression: q[r] = e4m3(x[r] * inv[r]), scale[r] = amax(x[r]) / 448,
+    inv[r] = 448 / amax(x[r]): both quotients IEEE-rounded fp32, the product one fp32 multiply,
+    the e4m3 rounding to nearest with ties to even (tests/_fp8_oracle.py is the exact reference
+    of both paths). A row with amax < FP8_TINY_AMAX (2^-110) is sent as a zero row (scale = 0,
+    codes +-0, dequantised +-0): 448 / amax overflows below ~1.3e-36 and would turn the row into
+    NaN. A NaN or +-inf element comes back non-finite at its position; a row holding one is not
+    otherwise specified. x bf16 [rows][cols], q uint8 [rows][>=cols], scale fp32 [rows]."""
     rows, cols = x.shape
     if q.dtype != torch.uint8 or q.shape[0] < rows or q.shape[1] < cols or scale.numel() < rows:
         raise ValueError("quant_rows_fp8: q must be uint8 [rows][>=cols], scale fp32 [>=rows]")
     if not x.is_cuda:
         xf = x.float()
         amax = xf.abs().amax(1)
-        inv = torch.where(amax > 0, FP8_MAX / amax, torch.zeros_like(amax))
+        send = amax >= FP8_TINY_AMAX  # False for a zero row and for a NaN amax
+        zero, top = torch.zeros_like(amax), torch.full_like(amax, FP8_MAX)
+        # tensor / tensor is the correctly rounded quotient; scalar / tensor multiplies by a
+        # reciprocal and is one ulp off in a quarter of the rows
+        inv = torch.where(send, top / amax, zero)
         q[:rows, :cols] = (xf * inv[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
-        scale[:rows] = amax / FP8_MAX
+        scale[:rows] = torch.where(send, amax / top, zero)
         return
     _rows(x, "x", torch.bfloat16)
     native().quant_rows_fp8(_p(x), x.stride(0), rows, cols, _p(q), q.stride(0), _p(scale),

@@ -694,9 +694,10 @@ def test_transpose_multi(dev):
 @pytest.mark.parametrize("rows,cols", [(1, 64), (300, 512), (64, 1024), (33, 136)])
 def test_fp8_boundary_kernels_match_reference(dev, rows, cols):
     """gfx950 e4m3 row quantisation (v_cvt_pk_fp8_f32, OCP encoding) vs torch float8_e4m3fn:
-    identical scales; codes identical except rare one-step rounding ties (the hardware and
-    torch's software conversion may break exact ties / subnormal rounding differently), so
-    the dequantised values agree within one e4m3 step."""
+    identical scales and identical codes. (The 0.2 % of codes that used to differ came from the
+    CPU path's reciprocal -- 448 * (1 / amax) instead of the IEEE quotient the kernel computes,
+    one ulp off in a quarter of the rows -- not from ties: both round ties to even. The exact
+    definition of the format is tests/_fp8_oracle.py.)"""
     gen = torch.Generator().manual_seed(rows * cols)
     x = (torch.randn(rows, cols, generator=gen) * 3).to(torch.bfloat16)
     if rows > 2:
@@ -708,7 +709,7 @@ def test_fp8_boundary_kernels_match_reference(dev, rows, cols):
     s_g = torch.empty(rows, device=dev)
     ops.quant_rows_fp8(xd, q_g, s_g)
     assert torch.equal(s_g.cpu(), s_c)
-    assert (q_g.cpu() != q_c).float().mean() < 2e-3
+    assert torch.equal(q_g.cpu(), q_c)
     y_c, y_g = torch.empty_like(x), torch.empty_like(xd)
     ops.dequant_rows_fp8(q_c, s_c, y_c)
     ops.dequant_rows_fp8(q_g, s_g, y_g)
