@@ -48,7 +48,7 @@ class _RankSteps:
             st = ex.stages[0]
             st.begin_step()
             if st.params.fused_layers:  # one-split wgrads update in their epilogue
-                st.params.set_lr(ex.lr_fn() if ex.lr_fn else st.params.optim.lr)
+                st.params.opt.arm(ex.lr_fn() if ex.lr_fn else None)
         for s, op, jj in self.order:
             ex = self.execs[s]
             ex._run_op(ex.stages[0], op, jj, None)

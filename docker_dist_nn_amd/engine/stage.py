@@ -21,374 +21,19 @@ head's business (engine/loss_head.py); a Stage only asks the head which layers i
 """
 from __future__ import annotations
 
-import math
-import os
-from dataclasses import dataclass
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
 
 from .. import ops
-from ..models.mlp import LayerGeom, MLPSpec, round_up
+from ..models.mlp import LayerGeom, MLPSpec
 from ..utils.native import native
 from .. import switches
 from .loss_head import LossHead, check_loss
+from .optimizer import OptimConfig  # (tests and bench scripts import both from this module)
+from .params import StageParams
 
-_ALIGN = 64  # elements; keeps every layer's region 256-B aligned
 RELU_MASK_AUTO_WIDTH = 1024  # DNN_RELU_MASK=auto: masks for hidden layers at least this wide
-
-
-@dataclass
-class OptimConfig:
-    name: str = "sgd"
-    lr: float = 0.05
-    momentum: float = 0.0
-    weight_decay: float = 0.0
-    betas: tuple[float, float] = (0.9, 0.999)
-    eps: float = 1e-8
-    decoupled: bool = False
-
-
-class StageParams:
-    """Flat parameter / gradient / optimizer buffers of a stage's layers."""
-
-    def __init__(self, geoms: Sequence[LayerGeom], device: torch.device,
-                 optim: Optional[OptimConfig] = None, shard: Optional[tuple[int, int]] = None):
-        self.geoms = list(geoms)
-        self.device = device
-        self.optim = optim or OptimConfig()
-        # sharded data parallelism (shard = (dp, dp_rank), see shard_piece): every layer's
-        # region ends on a multiple of dp * _ALIGN, so any bucket of whole layers splits into
-        # dp equal, aligned pieces
-        self.sharded = shard is not None
-        self.dp, self.dp_rank = shard or (1, 0)
-        off = 0
-        self.w_off, self.b_off = [], []
-        if self.sharded:
-            # weights first, each padded to dp pieces; then every bias (replicated update)
-            for g in self.geoms:
-                self.w_off.append(off)
-                off = round_up(off + g.np_ * g.kp, _ALIGN * self.dp)
-            self.bias_lo = off
-            for g in self.geoms:
-                self.b_off.append(off)
-                off = round_up(off + g.np_, _ALIGN)
-        else:
-            for g in self.geoms:
-                self.w_off.append(off)
-                off = round_up(off + g.np_ * g.kp, _ALIGN)
-                self.b_off.append(off)
-                off = round_up(off + g.np_, _ALIGN)
-        self.numel = off
-        self.master = torch.zeros(off, dtype=torch.float32, device=device)
-        self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=device)
-        self.grad = torch.zeros(off, dtype=torch.float32, device=device)
-        if self.sharded:
-            # bf16 gradient (reduce-scatter input) and the reduced pieces this rank owns: the
-            # piece of bucket [e0, e1) lives at [e0 / dp, e1 / dp) of grad_piece
-            self.grad16 = torch.zeros(off, dtype=torch.bfloat16, device=device)
-            self.grad_piece = torch.zeros(off // self.dp, dtype=torch.bfloat16, device=device)
-            self.shard_buckets: list[tuple[int, int]] = []
-        self.state: list[torch.Tensor] = []
-        self.step_count = 0
-        # transposed bf16 weight shadows W^T[Kp][Np] of the layers whose dgrad reads them
-        # (enable_wt); refreshed after every update of their layer (refresh_t)
-        self.wt: dict[int, torch.Tensor] = {}
-        # layers whose weight gradient GEMM applies the SGD step itself (Stage.enable_fused_
-        # wgrad_update): the per-step update paths below skip their weights and W^T
-        self.fused_layers: set[int] = set()
-        self._init_state()
-
-    def _init_state(self):
-        o = self.optim
-        if o.name == "sgd":
-            self.state = [torch.zeros_like(self.master)] if o.momentum else []
-        elif o.name in ("adam", "adamw"):
-            self.state = [torch.zeros_like(self.master), torch.zeros_like(self.master)]
-        else:
-            raise ValueError(f"unknown optimizer {o.name!r} (sgd | adam | adamw)")
-
-    # views ------------------------------------------------------------------------------
-    def w32(self, i):
-        g = self.geoms[i]
-        return self.master[self.w_off[i]:self.w_off[i] + g.np_ * g.kp].view(g.np_, g.kp)
-
-    def b32(self, i):
-        return self.master[self.b_off[i]:self.b_off[i] + self.geoms[i].np_]
-
-    def wbf(self, i):
-        g = self.geoms[i]
-        return self.shadow[self.w_off[i]:self.w_off[i] + g.np_ * g.kp].view(g.np_, g.kp)
-
-    def gw(self, i):
-        g = self.geoms[i]
-        return self.grad[self.w_off[i]:self.w_off[i] + g.np_ * g.kp]
-
-    def gb(self, i):
-        return self.grad[self.b_off[i]:self.b_off[i] + self.geoms[i].np_]
-
-    def layer_grad_range(self, i) -> tuple[int, int]:
-        """Flat [start, end) of layer i's W and b gradients (a DP all-reduce bucket). Sharded
-        layout: layer i's WEIGHTS only (the biases live together at [bias_lo, numel))."""
-        if self.sharded:
-            return self.w_off[i], (self.w_off[i + 1] if i + 1 < len(self.geoms)
-                                   else self.bias_lo)
-        end = self.w_off[i + 1] if i + 1 < len(self.geoms) else self.numel
-        return self.w_off[i], end
-
-    # weights in/out -----------------------------------------------------------------------
-    def load(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray]) -> None:
-        """Set from unpadded [out][in] weights / [out] biases (any float dtype)."""
-        self.master.zero_()
-        for i, g in enumerate(self.geoms):
-            w = torch.as_tensor(np.asarray(weights[i], dtype=np.float32))
-            b = torch.as_tensor(np.asarray(biases[i], dtype=np.float32))
-            if tuple(w.shape) != (g.spec.out_dim, g.spec.in_dim):
-                raise ValueError(f"layer {g.index}: weight shape {tuple(w.shape)} != "
-                                 f"{(g.spec.out_dim, g.spec.in_dim)}")
-            self.w32(i)[:g.spec.out_dim, :g.spec.in_dim] = w.to(self.device)
-            self.b32(i)[:g.spec.out_dim] = b.to(self.device)
-        self.refresh_shadow()
-
-    def init_default(self, seed: int) -> None:
-        """nn.Linear default init, U(-1/sqrt(in), 1/sqrt(in)); seeded by GLOBAL layer index so
-        any stage split of the same model starts from identical weights."""
-        ws, bs = [], []
-        for g in self.geoms:
-            gen = torch.Generator().manual_seed(seed * 7919 + g.index)
-            bound = 1.0 / math.sqrt(g.spec.in_dim)
-            ws.append((torch.rand(g.spec.out_dim, g.spec.in_dim, generator=gen) * 2 - 1) * bound)
-            bs.append((torch.rand(g.spec.out_dim, generator=gen) * 2 - 1) * bound)
-        self.load([w.numpy() for w in ws], [b.numpy() for b in bs])
-
-    def refresh_shadow(self) -> None:
-        self.shadow.copy_(self.master.to(torch.bfloat16))
-        self.refresh_t()
-
-    def enable_wt(self, i: int) -> None:
-        g = self.geoms[i]
-        if i not in self.wt:
-            self.wt[i] = torch.zeros(g.kp, g.np_, dtype=torch.bfloat16, device=self.device)
-            ops.transpose_bf16(self.wbf(i), self.wt[i])
-
-    def refresh_t(self, a: int = 0, b: Optional[int] = None, step: bool = False,
-                  skip: frozenset = frozenset()) -> None:
-        """Re-derive W^T of the local layers [a, b) that keep one (after their update).
-        ``step``: a per-step update -- layers updated by their wgrad epilogue (which writes
-        W^T itself) are skipped; so are the ``skip`` layers (W^T written by the update)."""
-        b = len(self.geoms) if b is None else b
-        ops.transpose_multi([(self.wbf(i), self.wt[i]) for i in range(a, b) if i in self.wt and
-                             i not in skip and not (step and i in self.fused_layers)])
-
-    def _layers_of(self, e0: int, e1: int) -> tuple[int, int]:
-        """Local layers whose parameters lie in the flat element range [e0, e1)."""
-        ls = [i for i in range(len(self.geoms)) if self.w_off[i] < e1 and
-              self.b_off[i] + self.geoms[i].np_ > e0]
-        return (ls[0], ls[-1] + 1) if ls else (0, 0)
-
-    def _export_flat(self, buf: torch.Tensor) -> tuple[list[np.ndarray], list[np.ndarray]]:
-        ws, bs = [], []
-        for i, g in enumerate(self.geoms):
-            w = buf[self.w_off[i]:self.w_off[i] + g.np_ * g.kp].view(g.np_, g.kp)
-            ws.append(w[:g.spec.out_dim, :g.spec.in_dim].detach().cpu().numpy().copy())
-            bs.append(buf[self.b_off[i]:self.b_off[i] + g.spec.out_dim]
-                      .detach().cpu().numpy().copy())
-        return ws, bs
-
-    def export(self) -> tuple[list[np.ndarray], list[np.ndarray]]:
-        return self._export_flat(self.master)
-
-    def export_state(self, k: int) -> tuple[list[np.ndarray], list[np.ndarray]]:
-        """Unpadded per-layer view of optimizer state buffer k (momentum / Adam m, v)."""
-        return self._export_flat(self.state[k])
-
-    def load_state(self, k: int, weights: Sequence[np.ndarray],
-                   biases: Sequence[np.ndarray]) -> None:
-        """Set optimizer state buffer k from unpadded per-layer arrays (padding stays 0)."""
-        buf = self.state[k]
-        buf.zero_()
-        for i, g in enumerate(self.geoms):
-            w = torch.as_tensor(np.asarray(weights[i], dtype=np.float32))
-            b = torch.as_tensor(np.asarray(biases[i], dtype=np.float32))
-            if tuple(w.shape) != (g.spec.out_dim, g.spec.in_dim):
-                raise ValueError(f"layer {g.index}: state shape {tuple(w.shape)} != "
-                                 f"{(g.spec.out_dim, g.spec.in_dim)}")
-            view = buf[self.w_off[i]:self.w_off[i] + g.np_ * g.kp].view(g.np_, g.kp)
-            view[:g.spec.out_dim, :g.spec.in_dim] = w.to(self.device)
-            buf[self.b_off[i]:self.b_off[i] + g.spec.out_dim] = b.to(self.device)
-
-    # optimizer ----------------------------------------------------------------------------
-    def _device_scalars(self) -> None:
-        if getattr(self, "lr_dev", None) is None:
-            self.lr_dev = torch.full((1,), float(self.optim.lr), dtype=torch.float32,
-                                     device=self.device)
-            self.step_dev = torch.full((1,), int(self.step_count), dtype=torch.int32,
-                                       device=self.device)
-            self._lr_cur = float(self.optim.lr)
-
-    def set_lr(self, lr: float) -> None:
-        """Learning rate of the device-scalar (recorded) update path."""
-        self._device_scalars()
-        if float(lr) != self._lr_cur:
-            self.lr_dev.fill_(float(lr))
-            self._lr_cur = float(lr)
-
-    def set_step(self, n: int) -> None:
-        """Number of updates done (checkpoint resume): host counter and device counter."""
-        self.step_count = int(n)
-        if getattr(self, "step_dev", None) is not None:
-            self.step_dev.fill_(int(n))
-
-    def _unfused_ranges(self) -> list[tuple[int, int]]:
-        """[0, numel) minus the weight regions of fused_layers (updated by their wgrad)."""
-        cuts = sorted((self.w_off[i], self.w_off[i] + self.geoms[i].np_ * self.geoms[i].kp)
-                      for i in self.fused_layers)
-        out, lo = [], 0
-        for a, b in cuts:
-            if a > lo:
-                out.append((lo, a))
-            lo = b
-        if lo < self.numel:
-            out.append((lo, self.numel))
-        return out
-
-    def record_update(self) -> None:
-        """The launches of one optimizer update reading lr / step from device memory (for
-        recording into a native Program: no per-step host values)."""
-        self._device_scalars()
-        o = self.optim
-        if self.fused_layers:  # SGD only (Stage.enable_fused_wgrad_update)
-            for a, b in self._unfused_ranges():
-                sl = slice(a, b)
-                ops.sgd_update(self.master[sl], self.grad[sl],
-                               self.state[0][sl] if self.state else None, self.shadow[sl],
-                               lr=o.lr, momentum=o.momentum, weight_decay=o.weight_decay,
-                               lr_dev=self.lr_dev)
-            self.refresh_t(step=True)
-            return
-        if o.name == "sgd":
-            ops.sgd_update(self.master, self.grad, self.state[0] if self.state else None,
-                           self.shadow, lr=o.lr, momentum=o.momentum,
-                           weight_decay=o.weight_decay, lr_dev=self.lr_dev)
-        else:
-            ops.adam_update(self.master, self.grad, self.state[0], self.state[1], self.shadow,
-                            lr=o.lr, betas=o.betas, eps=o.eps, weight_decay=o.weight_decay,
-                            decoupled=o.decoupled or o.name == "adamw", lr_dev=self.lr_dev,
-                            step_dev=self.step_dev)
-            ops.step_advance(self.step_dev)
-        self.refresh_t(step=True)
-
-    def record_update_range(self, a: int, b: int, advance: bool, refresh: bool = True) -> None:
-        """record_update over the flat element range [a, b) only (a DP bucket of whole layers);
-        the device step counter advances only when ``advance`` (once per step: the last range
-        of a split update). ``refresh=False``: leave W^T alone (a shard piece, whose layers are
-        complete only after the all-gather)."""
-        self._device_scalars()
-        o = self.optim
-        sl = slice(a, b)
-        if o.name == "sgd":
-            ops.sgd_update(self.master[sl], self.grad[sl], self.state[0][sl] if self.state else None,
-                           self.shadow[sl], lr=o.lr, momentum=o.momentum,
-                           weight_decay=o.weight_decay, lr_dev=self.lr_dev)
-        else:
-            ops.adam_update(self.master[sl], self.grad[sl], self.state[0][sl], self.state[1][sl],
-                            self.shadow[sl], lr=o.lr, betas=o.betas, eps=o.eps,
-                            weight_decay=o.weight_decay,
-                            decoupled=o.decoupled or o.name == "adamw", lr_dev=self.lr_dev,
-                            step_dev=self.step_dev)
-        if advance and o.name != "sgd":
-            ops.step_advance(self.step_dev)
-        if refresh:
-            self.refresh_t(*self._layers_of(a, b))
-
-    # sharded data parallelism --------------------------------------------------------------
-    # Per bucket [e0, e1) of whole layers' WEIGHTS: the fp32 gradient is cast to bf16
-    # (shard_pack), reduce-scattered over the DP group (rank r receives the sum of piece r),
-    # cast back into grad[piece] (shard_unpack) and only that piece is updated (fp32 master +
-    # optimizer state of the piece are authoritative on this rank); the bf16 shadow is then
-    # all-gathered and W^T refreshed. The biases (fp32 in the GEMM epilogues, a few KB) are
-    # all-reduced in fp32 and updated on every rank. Bytes on the wire: 2 x (dp-1)/dp x 2 B per
-    # weight, half of an fp32 all-reduce, and the optimizer touches 1/dp of the weights.
-    def shard_piece(self, e0: int, e1: int) -> tuple[int, int]:
-        c = (e1 - e0) // self.dp
-        if c * self.dp != e1 - e0:
-            raise ValueError("bucket length is not a multiple of the DP degree")
-        return e0 + self.dp_rank * c, e0 + (self.dp_rank + 1) * c
-
-    def shard_pack(self, e0: int, e1: int) -> None:
-        ops.pack_bf16(self.grad[e0:e1].view(1, -1), self.grad16[e0:e1].view(1, -1))
-
-    def shard_unpack(self, e0: int, e1: int) -> None:
-        p0, p1 = self.shard_piece(e0, e1)
-        d = self.dp
-        ops.unpack_bf16(self.grad_piece[e0 // d:e1 // d].view(1, -1),
-                        self.grad[p0:p1].view(1, -1))
-
-    def gather_full(self, group) -> None:
-        """All-gather the fp32 master and optimizer state over the DP group: afterwards every
-        rank holds the whole (checkpoint / export); a no-op without sharding."""
-        if not self.sharded or not self.shard_buckets:
-            return
-        import torch.distributed as dist
-
-        for buf in [self.master] + list(self.state):
-            for e0, e1 in self.shard_buckets:
-                p0, p1 = self.shard_piece(e0, e1)
-                dist.all_gather_into_tensor(buf[e0:e1], buf[p0:p1].clone(), group=group)
-
-    def update_range(self, a: int, b: int, lr: Optional[float], advance: bool,
-                     refresh: bool = True) -> None:
-        """Optimizer update of the flat range [a, b) (see record_update_range); the host step
-        counter counts whole steps (advance=True)."""
-        o = self.optim
-        lr = o.lr if lr is None else lr
-        if self.device.type == "cuda":
-            self.set_lr(lr)
-            self.record_update_range(a, b, advance, refresh)
-        else:
-            sl = slice(a, b)
-            step = self.step_count + 1
-            if o.name == "sgd":
-                ops.sgd_update(self.master[sl], self.grad[sl],
-                               self.state[0][sl] if self.state else None, self.shadow[sl],
-                               lr=lr, momentum=o.momentum, weight_decay=o.weight_decay)
-            else:
-                ops.adam_update(self.master[sl], self.grad[sl], self.state[0][sl],
-                                self.state[1][sl], self.shadow[sl], lr=lr, betas=o.betas,
-                                eps=o.eps, weight_decay=o.weight_decay,
-                                decoupled=o.decoupled or o.name == "adamw", step=step)
-            if refresh:
-                self.refresh_t(*self._layers_of(a, b))
-        if advance:
-            self.step_count += 1
-
-    def layers_range(self, a: int, b: int) -> tuple[int, int]:
-        """Flat [start, end) of layers a..b-1 (weights, biases and alignment padding)."""
-        if self.sharded:
-            raise ValueError("sharded layout: layer ranges are not contiguous")
-        return self.w_off[a], (self.w_off[b] if b < len(self.geoms) else self.numel)
-
-    def optimizer_step(self, lr: Optional[float] = None) -> None:
-        o = self.optim
-        lr = o.lr if lr is None else lr
-        if self.device.type == "cuda":
-            # GPU: lr and step always come from device memory, so the same launches are valid
-            # eagerly, recorded into a native Program, or captured in a HIP graph (by-value
-            # Adam bias corrections would be frozen by a capture)
-            self.set_lr(lr)
-            self.record_update()
-            self.step_count += 1
-            return
-        self.step_count += 1
-        if o.name == "sgd":
-            ops.sgd_update(self.master, self.grad, self.state[0] if self.state else None,
-                           self.shadow, lr=lr, momentum=o.momentum, weight_decay=o.weight_decay)
-        else:
-            ops.adam_update(self.master, self.grad, self.state[0], self.state[1], self.shadow,
-                            lr=lr, betas=o.betas, eps=o.eps, weight_decay=o.weight_decay,
-                            decoupled=o.decoupled or o.name == "adamw", step=self.step_count)
-        self.refresh_t(step=True)
 
 
 def _of_head(path: str, default=None) -> property:
@@ -746,13 +391,7 @@ class Stage:
             if i in p.fused_layers:  # the epilogue applies SGD to W_i and writes W_i^T
                 if j >= 0:
                     raise RuntimeError("fused weight update runs on the batched wgrad only")
-                p._device_scalars()
-                g, o = self.geoms[i], p.optim
-                w0, w1 = p.w_off[i], p.w_off[i] + g.np_ * g.kp
-                upd = dict(master=p.w32(i), shadow=p.wbf(i), lr_dev=p.lr_dev,
-                           mom=p.state[0][w0:w1].view(g.np_, g.kp) if p.state else None,
-                           momentum=o.momentum, weight_decay=o.weight_decay)
-                wt = p.wt.get(i)
+                upd, wt = p.epilogue_args(i), p.wt.get(i)
             ops.linear_wgrad(self.dz[i][r], self.input_of(i)[r], self.slabs[i],
                              splits=self.w_splits[i], accumulate=accumulate,
                              dzt=self.dzT[i] if kk else None,
@@ -807,51 +446,35 @@ class Stage:
     def fused_fin_sgd_ok(self) -> bool:
         """FIN + optimizer step as one launch: every gradient element must come out of a reduce
         job (not stream-K wgrad, which writes weight gradients directly); SGD, Adam or AdamW."""
-        return (self.params.optim.name in ("sgd", "adam", "adamw") and
-                self.wgrad_algo != "streamk" and self.device.type == "cuda" and
+        return (self.wgrad_algo != "streamk" and self.device.type == "cuda" and
                 switches.get("DNN_FUSE_FIN_SGD") == "1")
 
     def _record_fin_sgd(self, a: int = 0, b: Optional[int] = None) -> None:
-        """Record the gradient reduction of local layers [a, b) (default: all) with the SGD
-        update fused in (segment FINO, or FINO{a}-{b-1} for a layer range: SGD only, so the
-        step counter needs no advance; lr from device memory like record_update)."""
+        """Record the gradient reduction of local layers [a, b) (default: all) with the
+        optimizer update fused in (segment FINO, or FINO{a}-{b-1} for a layer range: SGD only,
+        so the step counter needs no advance; lr from device memory like every update)."""
         p = self.params
-        p._device_scalars()
-        o = p.optim
         L = len(self.geoms)
         b = L if b is None else b
+        if not p.opt.is_sgd and (a, b) != (0, L):
+            raise ValueError("layer-range fused updates are SGD only")
         wt_fused = switches.get("DNN_FIN_WT") == "1" and p.shadow is not None
         jobs = self._jobs(tuple(range(a, b)), with_wt=wt_fused)
         # layers whose W^T comes out of the update launch itself (no transpose launch after it)
         skip = frozenset(i for i in self._wt_by_update_layers()) if wt_fused else frozenset()
-        if o.name == "sgd":
-            ops.reduce_multi(jobs, sgd=dict(grad=p.grad, master=p.master,
-                                            mom=p.state[0] if p.state else None,
-                                            shadow=p.shadow, lr=o.lr, momentum=o.momentum,
-                                            weight_decay=o.weight_decay, lr_dev=p.lr_dev))
-            p.refresh_t(a, b, step=True, skip=skip)
-            return
-        if (a, b) != (0, L):
-            raise ValueError("layer-range fused updates are SGD only")
-        ops.reduce_multi(jobs, sgd=dict(grad=p.grad, master=p.master, mom=p.state[0],
-                                        v=p.state[1], shadow=p.shadow, lr=o.lr,
-                                        weight_decay=o.weight_decay, lr_dev=p.lr_dev,
-                                        adam=True, betas=o.betas, eps=o.eps,
-                                        decoupled=o.decoupled or o.name == "adamw",
-                                        step_dev=p.step_dev))
-        ops.step_advance(p.step_dev)  # as record_update: the segment replaces FIN + O
-        p.refresh_t(step=True, skip=skip)
+        ops.reduce_multi(jobs, sgd=p.opt.fused_args())
+        p.opt.record_advance()  # Adam (whole step only): the segment replaces FIN + O
+        p.refresh_t(a, b, step=True, skip=skip)
 
     def update_then_forward(self, j: int, s: int, lr: Optional[float] = None) -> None:
         """Deferred DP update of layers [s, L) (completing the step: advance) followed by the
         forward of micro-batch j through [s, L) -- ONE native call when recorded."""
         L = len(self.geoms)
         if self._prog is not None and self._o_native and not self._recording:
-            p = self.params
-            p.set_lr(p.optim.lr if lr is None else lr)
+            self.params.opt.arm(lr)
             self._prog.run([f"O{s}-{L}", "OADV"] + [f"F{j}.L{i}" for i in range(s, L)],
                            torch.cuda.current_stream(self.device).cuda_stream)
-            p.step_count += 1
+            self.params.opt.commit()
             return
         self.update_layers(s, L, lr, advance=True)
         self.forward_layers(j, s, L)
@@ -880,7 +503,7 @@ class Stage:
         before compile_native. Returns the layers."""
         p = self.params
         if (self.device.type != "cuda" or self.wgrad_mode != "batched" or
-                self.wgrad_algo != "splitk" or p.optim.name != "sgd" or p.sharded or
+                self.wgrad_algo != "splitk" or not p.opt.is_sgd or p.sharded or
                 switches.get("DNN_WGRAD_FUSED_UPDATE") == "0" or self._prog is not None):
             return []
         p.fused_layers = {i for i in range(len(self.geoms)) if self.w_splits[i] == 1}
@@ -891,36 +514,37 @@ class Stage:
         """Sharded DP: unpack this rank's reduced piece of bucket [e0, e1) and update it (no
         step advance, no W^T refresh: both follow once per step)."""
         p = self.params
+        p.opt.arm(lr)
         p.shard_unpack(e0, e1)
-        p0, p1 = p.shard_piece(e0, e1)
-        p.update_range(p0, p1, lr, advance=False, refresh=False)
+        p.update_range(*p.shard_piece(e0, e1), advance=False, refresh=False)
 
     def bias_update(self, lr: Optional[float] = None) -> None:
         """Sharded DP: every rank updates all biases (their fp32 gradients are all-reduced)."""
         p = self.params
-        p.update_range(p.bias_lo, p.numel, lr, advance=False, refresh=False)
+        p.opt.arm(lr)
+        p.update_range(p.bias_lo, p.numel, advance=False, refresh=False)
 
     def update_layers(self, a: int, b: int, lr: Optional[float] = None,
                       advance: bool = True) -> None:
         """Optimizer update of local layers [a, b) only (``advance``: this completes the
         step's update -- Adam's step counter moves once per step)."""
+        p = self.params
+        p.opt.arm(lr)
         if self._prog is not None and self._o_native and not self._recording:
-            p = self.params
-            p.set_lr(p.optim.lr if lr is None else lr)
             segs = [f"O{a}-{b}"] + (["OADV"] if advance else [])
             self._prog.run(segs, torch.cuda.current_stream(self.device).cuda_stream)
-            if advance:
-                p.step_count += 1
-            return
-        e0, e1 = self.params.layers_range(a, b)
-        self.params.update_range(e0, e1, lr, advance)
+        else:
+            p.update_range(*p.layers_range(a, b), advance)
+        if advance:
+            p.opt.commit()
 
     def optimizer_step(self, lr: Optional[float] = None) -> None:
+        self.params.opt.arm(lr)
         if self._prog is not None and self._o_native and not self._recording:
-            self.params.set_lr(self.params.optim.lr if lr is None else lr)
-            self.params.step_count += 1
-            return self._replay("O")
-        self.params.optimizer_step(lr)
+            self._replay("O")
+        else:
+            self.params.update()
+        self.params.opt.commit()
 
     def fuse_boundary_colsum(self, consumer: "Stage") -> None:
         """Same-process pipeline: ``consumer`` (the next stage) writes our last layer's
@@ -1005,7 +629,7 @@ class Stage:
             if self.fused_fin_sgd_ok():
                 prog.mark("FINO")
                 self._record_fin_sgd()
-                if self.params.optim.name == "sgd" and L > 1:
+                if self.params.opt.is_sgd and L > 1:
                     # per-layer-range forms: the overlap plan updates the small layers on the
                     # side stream while the big layer's wgrad still runs (DNN_SPLIT_FINO)
                     for a in range(L):
@@ -1013,18 +637,16 @@ class Stage:
                             prog.mark(f"FINO{a}-{b}")
                             self._record_fin_sgd(a, b + 1)
             prog.mark("O")
-            self.params.record_update()
-            for a in range(L if not (self.params.sharded or self.params.fused_layers) else 0):
+            p = self.params
+            p.update()
+            for a in range(L if not (p.sharded or p.fused_layers) else 0):
                 # split updates: every contiguous layer range, no step advance
                 for b in range(a + 1, L + 1):
                     prog.mark(f"O{a}-{b}")
-                    e0, e1 = self.params.layers_range(a, b)
-                    self.params.record_update_range(e0, e1, advance=False)
+                    p.update_range(*p.layers_range(a, b), advance=False)
             prog.mark("OADV")
-            if self.params.optim.name != "sgd":
-                ops.step_advance(self.params.step_dev)
-            if self.params.sharded:  # sharded DP: per bucket pack / unpack + piece update
-                p = self.params
+            p.opt.record_advance()
+            if p.sharded:  # sharded DP: per bucket pack / unpack + piece update
                 for a in range(L):
                     for b in range(a, L):
                         e0, _ = p.layer_grad_range(a)

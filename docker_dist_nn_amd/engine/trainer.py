@@ -349,11 +349,7 @@ class Trainer:
         out = []
         for st in self.stages:
             p = st.params
-            out += [p.master, p.shadow, *p.state, *p.wt.values()]
-            for name in ("lr_dev", "step_dev"):
-                t = getattr(p, name, None)
-                if isinstance(t, torch.Tensor):
-                    out.append(t)
+            out += [p.master, p.shadow, *p.wt.values(), *p.opt.tensors()]
         return out
 
     def _verify_first_step(self) -> None:
@@ -388,7 +384,7 @@ class Trainer:
         for t, v in zip(state, snap):
             t.copy_(v)
         for st, c in zip(self.stages, counts):
-            st.params.step_count = c
+            st.params.opt.restore_count(c)
         ipc_ns, ipc_pipe = self.native_step, self.pipe
         fb = self._ipc_verify[1]
         self.executor.native_step = self._fallback_step
@@ -449,7 +445,7 @@ class Trainer:
         if self._graph is not None:
             cur = torch.cuda.current_stream(self.device)
             for st in self.stages:  # the captured update reads the learning rate from device
-                st.params.set_lr(st.params.optim.lr)
+                st.params.opt.arm()
             self._stream.wait_stream(cur)  # inputs (and lr) written on the caller's stream
             # alternate between identical instantiations: relaunching the SAME exec before its
             # previous launch retired makes the host wait (measured ~130 us idle per step)
@@ -457,7 +453,7 @@ class Trainer:
             g.replay(self._stream.cuda_stream)
             cur.wait_stream(self._stream)
             for st in self.stages:  # the captured update advanced the device step counter
-                st.params.step_count += 1
+                st.params.opt.commit()
         elif self._ipc_verify is not None:
             self._verify_first_step()
         else:
@@ -523,7 +519,7 @@ class Trainer:
                 graphs.append(g)
             graphs[0].replay(self._stream.cuda_stream)  # capture itself executes nothing
         for st, c in zip(self.stages, counts):  # `copies` captures, ONE executed step
-            st.params.step_count = c + 1
+            st.params.opt.restore_count(c + 1)
         cur.wait_stream(self._stream)
         self._graphs = graphs
         self._graph = graphs[0]

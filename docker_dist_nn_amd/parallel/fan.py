@@ -1092,10 +1092,10 @@ def _fan_native_step_class():
             if not self.colo:
                 return NativeStep.run(self, stream)
             for st in self.stages_all:
-                st.params.set_lr(st.params.optim.lr)
+                st.params.opt.arm()
             self.plan.run(stream)
             for st in self.stages_all:
-                st.params.step_count += 1
+                st.params.opt.commit()
 
         def _base(self, name: str) -> int:
             """First global rank of the boundary group a link channel lives on."""

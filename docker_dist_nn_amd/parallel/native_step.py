@@ -343,7 +343,7 @@ class NativeStep:
             self.ops.append(dict(kind=ALL_GATHER, stream=dps, comm=dpc,
                                  a=p.shadow.data_ptr() + 2 * p0, b=p.shadow.data_ptr() + 2 * e0,
                                  count=(e1 - e0) // d, dtype=NCCL_BF16))
-        if p.optim.name != "sgd":
+        if not p.opt.is_sgd:
             self._seg("OADV")
         self._edge(dps, MAIN)
         self._seg("T")
@@ -561,14 +561,14 @@ class NativeStep:
 
     # ---- execution -----------------------------------------------------------------------
     def run(self, stream: int) -> None:
-        p = self.st.params
-        p.set_lr(p.optim.lr)
+        opt = self.st.params.opt
+        opt.arm()
         if self.transport == "ipc":
             self.plan.seq = self.ipc.seq  # one sequence space with the Python IpcPipe
         self.plan.run(stream)
         if self.transport == "ipc":
             self.ipc.seq = self.plan.seq
-        p.step_count += 1
+        opt.commit()
 
     def comm_error(self) -> int:
         """RCCL async error of any communicator of the plan, or -1 if a flag wait (IPC hop)

@@ -228,12 +228,8 @@ class PipelineExecutor:
         for _, e0, e1 in buckets:
             st.shard_update(e0, e1, lr)
         st.bias_update(lr)
-        if p.optim.name != "sgd":  # the step's one device-counter advance (Adam)
-            if p.device.type == "cuda":
-                from .. import ops
-
-                ops.step_advance(p.step_dev)
-        p.step_count += 1
+        p.opt.record_advance()  # the step's one device-counter advance (Adam)
+        p.opt.commit()
         for _, e0, e1 in buckets:
             gs.all_gather_shadow(p, e0, e1)
         gs.wait()
@@ -508,7 +504,7 @@ class PipelineExecutor:
             if st.params.fused_layers:
                 # one-split wgrads apply SGD in their epilogue (W, before O): they read the
                 # device lr, so this step's rate must be there before any W
-                st.params.set_lr(self.lr_fn() if self.lr_fn else st.params.optim.lr)
+                st.params.opt.arm(self.lr_fn() if self.lr_fn else None)
         plan = self._native_plan()
         if plan is not None and len(self.stages) > 1 and not getattr(self, "capturing", False) \
                 and switches.get("DNN_LOOPBACK_STREAMS") == "1":
@@ -516,10 +512,10 @@ class PipelineExecutor:
                 self._lb_plan = self._loopback_step_plan(plan)
             if self._lb_plan is not None:
                 for st in self.stages:
-                    st.params.set_lr(st.params.optim.lr)
+                    st.params.opt.arm()
                 self._lb_plan.run(torch.cuda.current_stream(self.stages[0].device).cuda_stream)
                 for st in self.stages:
-                    st.params.step_count += 1
+                    st.params.opt.commit()
                 self.pipe.end_step()
                 return
         if plan is not None and len(self.stages) == 1 and \
@@ -531,13 +527,12 @@ class PipelineExecutor:
         if plan is not None:
             dev = self.stages[0].device
             if getattr(self, "_xprimed", False) and any(
-                    float(st.params.optim.lr) != getattr(st.params, "_lr_cur", None)
-                    for st in self.stages):
+                    st.params.opt.arm_writes() for st in self.stages):
                 # the previous step's side-stream update still reads lr_dev: a new rate is
                 # written only after it
                 self.xstep_join()
             for st in self.stages:
-                st.params.set_lr(st.params.optim.lr)
+                st.params.opt.arm()
             if self._side is None and (self.wgrad_streams > 1 or
                                        any(e[1] == "@fork" for e in plan)):
                 self._side = torch.cuda.Stream(dev)
@@ -548,7 +543,7 @@ class PipelineExecutor:
                               self._side.cuda_stream if self._side is not None else 0,
                               switches.get("DNN_EVENT_FENCE") == "device", id(self))
             for st in self.stages:
-                st.params.step_count += 1
+                st.params.opt.commit()
             self.pipe.end_step()
             return
         if len(self.stages) == 1:

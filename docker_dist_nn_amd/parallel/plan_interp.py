@@ -148,7 +148,7 @@ class PlanInterpreter:
     def run_step(self) -> None:
         ns = self.ns
         for st in self.stages:
-            st.params.set_lr(st.params.optim.lr)
+            st.params.opt.arm()
         ipc = getattr(ns, "ipc", None)
         nat = None
         if ipc is not None or any(o["kind"] == COPY for q in self.queues.values() for o in q):
@@ -209,7 +209,7 @@ class PlanInterpreter:
                     time.sleep(0.0005)
         torch.cuda.synchronize()
         for st in self.stages:
-            st.params.step_count += 1
+            st.params.opt.commit()
 
 
 def interp_groups(mesh, names: Optional[dict] = None) -> tuple[dict, dict]:

@@ -61,7 +61,7 @@ def _worker(rank, world, port, out):
     ops.append(dict(kind=ALL_GATHER, stream=3, comm=comms["dp"], a=f(shadow, mesh.replica * c),
                     b=f(shadow), count=c, dtype=NCCL_BF16))
     st = NS(device=torch.device("cpu"), x=x, g16=g16, piece=piece, shadow=shadow, bias=bias,
-            params=NS(set_lr=lambda lr: None, optim=NS(lr=0.1), step_count=0))
+            params=NS(opt=NS(arm=lambda lr=None: None, commit=lambda: None)))
     it = pi.PlanInterpreter.__new__(pi.PlanInterpreter)
     it.ns, it.groups, it.timeout = NS(st=st, ops=ops), groups, 30
     it.stages = [st]
