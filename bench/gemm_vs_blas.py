@@ -58,13 +58,13 @@ def main():
             rows.append(("fwd", ours, blas, 2 * (R * Kp + Np * Kp + R * Np)))
         if i > 0:
             dx = torch.empty(R, Kp, device=dev, dtype=torch.bfloat16)
-            bm = K_.dgrad_tiles(R, Kp, Np)[0]
+            bm = ops.dgrad_tiles(R, Kp, Np)[0]
             cs = torch.empty(-(-R // bm), Kp, device=dev)
             ours = timeit(lambda: K_.linear_dgrad(dz, w, dx, y_prev=x, act_prev="relu",
                                                   colsum=cs), a.iters)
             blas = timeit(lambda: torch.mm(dz, w, out=dx), a.iters)
             rows.append(("dgrad", ours, blas, 2 * (R * Np + Np * Kp + 2 * R * Kp)))
-        bm, bn, s = K_.wgrad_config(Np, Kp, R)
+        bm, bn, s = ops.wgrad_config(Np, Kp, R)
         slabs = torch.empty(s, Np, Kp, device=dev)
         ours = timeit(lambda: K_.linear_wgrad(dz, x, slabs, splits=s), a.iters)
         blas = timeit(lambda: torch.mm(dz.t(), x), a.iters)

@@ -1,6 +1,6 @@
 """Pipeline-depth x tile sweep of the GEMMs of one MNIST-FCNN training step (and of the wider
 benchmark models): time of every (op, shape) under NS = 2/3/4 LDS stages and each legal tile.
-Prints one JSON line per measurement; used to set ops.kernels.STAGES / the tile policy.
+Prints one JSON line per measurement; used to set ops.gemm_plan.STAGES / the tile policy.
 Random bf16 operands (never time zero-filled data)."""
 from __future__ import annotations
 

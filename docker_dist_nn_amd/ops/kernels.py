@@ -12,108 +12,21 @@ graph replays with fixed pointers) and dispatches on the device of its inputs:
 """
 from __future__ import annotations
 
-import math
-import os
-
 import torch
 
 from ..models.mlp import ACT_CODE
 from ..utils.native import native
 from . import reference as ref
-from . import tuning
 from .. import switches
+from .gemm_plan import (DIRECT_STAGES, FRAG_WAVES, GEMV_MAX_ROWS, GROUP_STAGES, NUM_CU,
+                        RP_STAGED, blas_built, pick_tiles, plan)  # noqa: F401 (blas_built: the
+# comparison build's blas_gemm / dact_colsum live here, and callers ask this module for it)
 
 KMAJ, MNMAJ = 0, 1
 
 
-def _parse_stages(spec: str) -> dict:
-    """DNN_GEMM_STAGES: "3" (every GEMM) or "fwd=3,dgrad=2,wgrad=4,xent=2"; 0 = kernel
-    default."""
-    out = {"fwd": 0, "dgrad": 0, "wgrad": 0, "xent": 0}
-    spec = spec.strip()
-    if not spec:
-        return out
-    if "=" not in spec:
-        return {k: int(spec) for k in out}
-    for part in spec.split(","):
-        k, v = part.split("=")
-        if k.strip() not in out:
-            raise ValueError(f"DNN_GEMM_STAGES: unknown GEMM kind {k!r}")
-        out[k.strip()] = int(v)
-    return out
-
-
-# LDS pipeline depth (2..4) per GEMM kind; see mma_tile in csrc/kernels/gemm.hip. 8 selects the
-# ping-pong half-tile-streamed form of the 256x256 tile (csrc/kernels/gemm_pp.hip).
-STAGES = _parse_stages(switches.get("DNN_GEMM_STAGES"))
 # A/B of the activation-specialised register-direct epilogue (GemmParams::epi_probe bit 2)
 _EPI_GENERIC = 4 if switches.get("DNN_GEMM_EPI_GENERIC") == "1" else 0
-
-
-def _parse_persist(spec: str) -> dict:
-    """DNN_GEMM_PERSIST: "" (tuned table decides), "0"/"1" (every GEMM off/on), or
-    "fwd=1,dgrad=0,wgrad=1"; a value > 1 is an explicit workgroup count. None = table."""
-    out = {"fwd": None, "dgrad": None, "wgrad": None}
-    spec = spec.strip()
-    if not spec:
-        return out
-    if "=" not in spec:
-        return {k: int(spec) for k in out}
-    for part in spec.split(","):
-        k, v = part.split("=")
-        if k.strip() not in out:
-            raise ValueError(f"DNN_GEMM_PERSIST: unknown GEMM kind {k!r}")
-        out[k.strip()] = int(v)
-    return out
-
-
-# Persistent-workgroup GEMM form (csrc/kernels/gemm_persist.hip) per GEMM kind.
-PERSIST = _parse_persist(switches.get("DNN_GEMM_PERSIST"))
-
-
-def _persist(kind: str, entry) -> int:
-    """Native `persist` argument: 0 = one tile per workgroup, -1 = one resident round of
-    persistent workgroups, > 1 = that many workgroups."""
-    v = PERSIST[kind]
-    if v is None:
-        v = (entry or {}).get("persist", 0)
-    return -1 if v == 1 else int(v)
-
-
-def _blas_requested(kind: str, entry) -> bool:
-    """Is the library (hipBLASLt) GEMM requested for this product? DNN_BLAS: "" / "table" = the
-    tuned table's ``blas`` flag, "0" = never, "1" = every product the library path supports,
-    or per kind ("fwd=1,dgrad=0,wgrad=1")."""
-    spec = switches.get("DNN_BLAS").strip()
-    if spec in ("", "table"):
-        return bool((entry or {}).get("blas", 0))
-    if "=" not in spec:
-        return spec == "1"
-    return dict(kv.split("=") for kv in spec.split(",")).get(kind, "0") == "1"
-
-
-_BLAS_WARNED = []
-
-
-def blas_built() -> bool:
-    """The library path exists only in the comparison build (``_build --blas``); the product
-    build links no vendor GEMM library."""
-    return bool(native().blas_available())
-
-
-def _blas(kind: str, entry) -> bool:
-    """Library GEMM for this product: requested (``_blas_requested``) AND built in."""
-    if not _blas_requested(kind, entry):
-        return False
-    if blas_built():
-        return True
-    if not _BLAS_WARNED:
-        _BLAS_WARNED.append(1)
-        import warnings
-
-        warnings.warn("DNN_BLAS asks for the hipBLASLt path, which is only in the comparison "
-                      "build (python -m docker_dist_nn_amd._build --blas): own kernels run")
-    return False
 
 
 _BLAS_OK: dict = {}
@@ -122,14 +35,11 @@ _BLAS_OK: dict = {}
 def _blas_ok(a, b, d, trans_a, trans_b, M, N, K, bias, relu, accumulate) -> bool:
     """Does hipBLASLt have an algorithm for this problem signature? (probed once per signature;
     a table entry that asks for the library falls back to the MFMA kernels when it has none)"""
-    key = (trans_a, trans_b, M, N, K, a.stride(0), b.stride(0), d.stride(-2),
-           d.dtype == torch.float32, bias is not None, relu, accumulate)
-    ok = _BLAS_OK.get(key)
-    if ok is None:
-        ok = _BLAS_OK[key] = bool(native().blas_supported(
-            int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0), d.stride(-2),
-            int(d.dtype == torch.float32), int(bias is not None), int(relu), int(accumulate)))
-    return ok
+    key = (int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0), d.stride(-2),
+           int(d.dtype == torch.float32), int(bias is not None), int(relu), int(accumulate))
+    if key not in _BLAS_OK:
+        _BLAS_OK[key] = bool(native().blas_supported(*key))
+    return _BLAS_OK[key]
 
 
 def blas_gemm(a, b, d, *, trans_a: bool, trans_b: bool, M: int, N: int, K: int, bias=None,
@@ -178,77 +88,6 @@ def _rows(t: torch.Tensor, name: str, dtype: torch.dtype) -> None:
 
 def _act(act) -> int:
     return ACT_CODE[act] if isinstance(act, str) else int(act)
-
-
-# Residency model for tile choice: LDS/regs admit 2 (128x128), 3 (128x64 / 64x128) or
-# 4 (64x64) 4-wave workgroups per CU, and one 8-wave workgroup of the 256-row/-column tiles;
-# relative per-CU throughput of the tile shapes.
-_TILE_OCC = {(128, 128): 2, (128, 64): 3, (64, 128): 3, (64, 64): 4,
-             (256, 256): 1, (256, 128): 1, (128, 256): 1, (256, 64): 1}
-_TILE_EFF = {(128, 128): 1.0, (128, 64): 0.82, (64, 128): 0.82, (64, 64): 0.62}
-BIG_TILES = [(256, 256), (256, 128), (128, 256), (256, 64)]
-NUM_CU = 256
-
-
-def pick_tiles(M: int, N: int, splits: int = 1) -> tuple[int, int]:
-    """Tile for a [M][N] output (fwd / dgrad, M = batch rows).
-
-    The 8-wave 256-row tiles stage half the LDS bytes per FLOP of the 128x128 tile and win
-    whenever they still give >= 2 workgroups per CU (bench/stage_sweep.py on MI355X): 256x256
-    for outputs >= 1024 wide, 256x64 for 128..1023. Otherwise: the 4-wave tile minimising
-    modelled time = rounds of resident tiles x per-tile cost."""
-    if splits == 1 and M % 256 == 0:
-        if N % 256 == 0 and N >= 1024 and (M // 256) * (N // 256) >= 2 * NUM_CU:
-            return 256, 256
-        if N % 64 == 0 and N >= 128 and (M // 256) * (N // 64) >= 2 * NUM_CU:
-            return 256, 64
-    best, best_t = None, math.inf
-    for (bm, bn) in _TILE_EFF:  # calibrated tiles only
-        if M % bm or N % bn:
-            continue
-        tiles = (M // bm) * (N // bn) * splits
-        # tiles resident on one CU share its matrix pipe: time ~ tiles per CU x tile cost
-        t = math.ceil(tiles / NUM_CU) * bm * bn / _TILE_EFF[(bm, bn)]
-        if t < best_t - 1e-9:
-            best, best_t = (bm, bn), t
-    if best is None:
-        raise ValueError(f"no tile divides M={M}, N={N} (pad to multiples of 64)")
-    return best
-
-
-def pick_splits(M: int, N: int, K_total: int, max_splits: int = 48) -> int:
-    """Split-K factor for the batch-contraction (wgrad) GEMM.
-
-    Splits may be uneven (k-ranges differ by at most one 64-step), so any S works. Resident
-    workgroups share a CU, so time ~ ceil(tiles*S / CUs) / S tile-times (wave quantisation);
-    each extra split adds an fp32 slab of M*N to write and re-read. E.g. 52 tiles: S=8 puts 2
-    workgroups on 160 CUs and 1 on 96 (81% busy); S=14 gives 2-3 per CU (95%)."""
-    return wgrad_config(M, N, K_total, max_splits)[2]
-
-
-def wgrad_config(M: int, N: int, K_total: int, max_splits: int = 48) -> tuple[int, int, int]:
-    """Joint (bm, bn, splits) choice for the batch-contraction GEMM (see pick_splits): the
-    tuned table's measured optimum when it has the shape, else the model below."""
-    t = tuning.lookup("wgrad", M, N, K_total)
-    if _blas("wgrad", t):  # the library GEMM contracts all rows in one fp32 output
-        return (t["tile"][0], t["tile"][1], 1) if t else (*pick_tiles(M, N), 1)
-    if t is not None:
-        return t["tile"][0], t["tile"][1], t["splits"]
-    ksteps = K_total // 64
-    slab_cost = 2.0 * M * N * 4 / 5.0e12 * 0.6e15 / NUM_CU  # slab bytes in tile-FLOP units
-    best, best_c = None, math.inf
-    for (bm, bn), eff in _TILE_EFF.items():
-        if M % bm or N % bn:
-            continue
-        tiles = (M // bm) * (N // bn)
-        tile_flops = 2.0 * bm * bn * K_total / eff
-        for s in range(1, min(max_splits, ksteps) + 1):
-            c = math.ceil(tiles * s / NUM_CU) / s * tile_flops + (s > 1) * s * slab_cost
-            if c < best_c * 0.995:
-                best, best_c = (bm, bn, s), c
-    if best is None:
-        raise ValueError(f"no tile divides [{M}][{N}]")
-    return best
 
 
 def gemm(a, b, c, *, layout_a: int, layout_b: int, M: int, N: int, K: int, bias=None, aux=None,
@@ -311,7 +150,7 @@ def gemm(a, b, c, *, layout_a: int, layout_b: int, M: int, N: int, K: int, bias=
                                                                     else c[0]).stride(0)):
                 raise ValueError(f"fused update: {k} must be [M][N] with C's row stride")
     if stages in DIRECT_STAGES and (ct is not None or upd is not None):
-        stages = 6  # the register-direct epilogue has neither: RP loop, staged epilogue
+        stages = RP_STAGED  # the register-direct epilogue has neither: same loop, staged
     if not a.is_cuda:
         ref.gemm(a, b, c, layout_a=layout_a, layout_b=layout_b, M=M, N=N, K=K, bias=bias,
                  aux=aux, act=act, accumulate=accumulate, splits=splits, colsum=colsum,
@@ -380,8 +219,6 @@ def gemm(a, b, c, *, layout_a: int, layout_b: int, M: int, N: int, K: int, bias=
 
 # ---- the three GEMMs of a Linear layer -----------------------------------------------------
 
-GEMV_MAX_ROWS = 8
-
 
 def gemv(x, w, bias, y, act="relu"):
     """Serving-size layer (1..8 rows): y[m][n] = act(x[m] . w[n] + bias[n]), one wave per
@@ -402,12 +239,6 @@ def gemv(x, w, bias, y, act="relu"):
     native().gemv_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(y), y.stride(0),
                        M, N, K, _act(act), int(y.dtype == torch.float32), _stream(x))
     return y
-
-
-# wave grid (WM, WN) of the register-direct tiles that take fragment-order masks (NB >= 4 bytes
-# per lane; gemm_rp.hip pick_rp)
-FRAG_WAVES = {(256, 256): (4, 2), (256, 128): (4, 2), (128, 128): (2, 2), (128, 64): (2, 2)}
-DIRECT_STAGES = (9, 11)
 
 
 class FragMask:
@@ -464,23 +295,6 @@ class FragMask:
         return out[:self.m, :self.n]
 
 
-def frag_mask_tiles(M: int, N: int, K: int, N_next: int) -> tuple[int, int] | None:
-    """Tile of a fragment-order mask between the forward [M][N] (contraction K) of a ReLU layer
-    and the dgrad that produces its dZ from the next layer's [M][N_next] gradient, or None when
-    those two GEMMs do not both run one register-direct tile shape (linear_fwd / linear_dgrad
-    pick their tiles and stage codes from the tuned table)."""
-    tf = tuning.lookup("fwd", M, N, K)
-    tiles = tuple(tf["tile"]) if tf else pick_tiles(M, N)
-    td = tuning.lookup("dgrad", M, N, N_next)
-    sf = STAGES["fwd"] or (tf or {}).get("stages", 0)
-    sd = STAGES["dgrad"] or (td or {}).get("stages", 0)
-    if M <= GEMV_MAX_ROWS or tiles != dgrad_tiles(M, N, N_next) or tiles not in FRAG_WAVES or \
-            sf not in DIRECT_STAGES or sd not in DIRECT_STAGES or M % tiles[0] or \
-            _blas("fwd", tf) or _blas("dgrad", td):
-        return None
-    return tiles
-
-
 def relu_mask_bits(mask: torch.Tensor, M: int, N: int) -> torch.Tensor:
     """Unpack a GEMM-written ReLU mask (uint8 [M][ld], row-block-major: the byte of row r,
     8-column chunk c is at flat index ((r // 16) * ld + c) * 16 + r % 16) into bool [M][N]."""
@@ -503,26 +317,13 @@ def linear_fwd(x, w, bias, y, act="relu", mask=None, yt=None):
                     ct=yt)
     if M <= GEMV_MAX_ROWS:
         return gemv(x, w, bias, y, act)
-    t = tuning.lookup("fwd", M, N, K)
-    if mask is None and act in ("relu", "linear", 0, 1) and _blas("fwd", t) and \
+    p = plan("fwd", M, N, K)
+    if mask is None and act in ("relu", "linear", 0, 1) and p.blas and \
             _blas_ok(x, w, y, False, True, M, N, K, bias, _act(act) == 1, False):
         return blas_gemm(x, w, y, trans_a=False, trans_b=True, M=M, N=N, K=K, bias=bias,
-                         relu=_act(act) == 1, algo=(t or {}).get("blas_algo", 0))
-    tiles = tuple(t["tile"]) if t else pick_tiles(M, N)
+                         relu=_act(act) == 1, algo=p.blas_algo)
     return gemm(x, w, y, layout_a=KMAJ, layout_b=KMAJ, M=M, N=N, K=K, bias=bias, act=act,
-                tiles=tiles, stages=STAGES["fwd"] or (t or {}).get("stages", 0),
-                persist=0 if (mask is not None or yt is not None) else _persist("fwd", t),
-                mask_out=mask, ct=yt)
-
-
-def xent_tiles(M: int, N: int) -> tuple[int, int]:
-    """Tile of the fused linear+softmax-CE GEMM: the whole padded row in one tile (bn == N)."""
-    if N not in (64, 128):
-        raise ValueError(f"fused cross-entropy supports 64 or 128 padded classes, got {N}")
-    bm = 128 if M % 128 == 0 and (M // 128) * 1 >= NUM_CU // 2 else 64
-    if M % bm:
-        raise ValueError("rows must be a multiple of 64")
-    return bm, N
+                mask_out=mask, ct=yt, **p.launch_args(mask=mask is not None, ct=yt is not None))
 
 
 def linear_fwd_xent(x, w, bias, dz, labels, n_cls, scale, loss_part=None, correct=None,
@@ -532,7 +333,8 @@ def linear_fwd_xent(x, w, bias, dz, labels, n_cls, scale, loss_part=None, correc
     colsum[M/bm][Np] = per-tile column sums of dz (the bias-gradient partials)."""
     M, K = x.shape
     N = w.shape[0]
-    bm, bn = xent_tiles(M, N)
+    p = plan("xent", M, N, K)
+    bm, bn = p.tiles
     if labels.dtype != torch.int32 or labels.numel() < M:
         raise ValueError("labels must be int32 with one entry per row")
     if loss_part is not None and loss_part.numel() < M // bm:
@@ -556,15 +358,8 @@ def linear_fwd_xent(x, w, bias, dz, labels, n_cls, scale, loss_part=None, correc
                        _p(bias), 0, 0, M, N, K, 0, 0, KMAJ, KMAJ, 0, bm, bn, 1, _stream(x),
                        _p(colsum), colsum.stride(0) if colsum is not None else 0, _p(labels),
                        int(n_cls), float(scale), _p(loss_part), _p(correct),
-                       stages=STAGES["xent"])
+                       stages=p.stages)
     return dz
-
-
-def dgrad_tiles(M: int, K: int, N: int = 0) -> tuple[int, int]:
-    """Tile shape used by linear_dgrad for an [M][K] output from an [M][N] gradient (fixes
-    the colsum partial count)."""
-    t = tuning.lookup("dgrad", M, K, N) if N else None
-    return tuple(t["tile"]) if t else pick_tiles(M, K, 1)
 
 
 def transpose_bf16(src, dst):
@@ -662,28 +457,20 @@ def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_pr
         y_prev, act_prev = None, "relu"
     elif y_prev is None:
         act_prev = "linear"
-    t = tuning.lookup("dgrad", M, K, N)
-    if mask_prev is None and dz.is_cuda and _blas("dgrad", t) and \
+    p = plan("dgrad", M, K, N)
+    if mask_prev is None and dz.is_cuda and p.blas and \
             _blas_ok(dz, w, dx, False, False, M, K, N, None, False, False):
-        blas_gemm(dz, w, dx, trans_a=False, trans_b=False, M=M, N=K, K=N,
-                  algo=(t or {}).get("blas_algo", 0))
-        n_part = -(-M // dgrad_tiles(M, K, N)[0])
+        blas_gemm(dz, w, dx, trans_a=False, trans_b=False, M=M, N=K, K=N, algo=p.blas_algo)
+        n_part = -(-M // p.tiles[0])
         if y_prev is not None and _act(act_prev) != 0:
             dact_colsum(dx, y_prev, act_prev, colsum, n_part)
         elif colsum is not None:
             colsum_partial(dx, colsum, n_part)
         return dx
-    if wt is not None and dz.is_cuda:
-        return gemm(dz, wt, dx, layout_a=KMAJ, layout_b=KMAJ, M=M, N=K, K=N, aux=y_prev,
-                    act=act_prev, tiles=dgrad_tiles(M, K, N), colsum=colsum,
-                    stages=STAGES["dgrad"] or (t or {}).get("stages", 0),
-                    persist=0 if (dxt is not None or mask_prev is not None)
-                    else _persist("dgrad", t), mask_in=mask_prev, ct=dxt)
-    return gemm(dz, w, dx, layout_a=KMAJ, layout_b=MNMAJ, M=M, N=K, K=N, aux=y_prev,
-                act=act_prev, tiles=dgrad_tiles(M, K, N), colsum=colsum,
-                stages=STAGES["dgrad"] or (t or {}).get("stages", 0),
-                persist=0 if (mask_prev is not None or dxt is not None)
-                else _persist("dgrad", t), mask_in=mask_prev, ct=dxt)
+    b, layout_b = (wt, KMAJ) if wt is not None and dz.is_cuda else (w, MNMAJ)
+    return gemm(dz, b, dx, layout_a=KMAJ, layout_b=layout_b, M=M, N=K, K=N, aux=y_prev,
+                act=act_prev, colsum=colsum, mask_in=mask_prev, ct=dxt,
+                **p.launch_args(mask=mask_prev is not None, ct=dxt is not None))
 
 
 def linear_wgrad(dz, x, slabs, splits=1, accumulate=False, dzt=None, xt=None, upd=None,
@@ -700,29 +487,18 @@ def linear_wgrad(dz, x, slabs, splits=1, accumulate=False, dzt=None, xt=None, up
     K = x.shape[1]
     if upd is not None and (splits != 1 or accumulate):
         raise ValueError("the fused weight update needs one split and no accumulation")
-    if dzt is not None and xt is not None and dz.is_cuda:
-        bm, bn, s = wgrad_config(N, K, R)
-        tiles = (bm, bn) if s == splits else pick_tiles(N, K, splits)
-        t = tuning.lookup("wgrad", N, K, R) if s == splits else None
-        return gemm(dzt, xt, slabs, layout_a=KMAJ, layout_b=KMAJ, M=N, N=K, K=R, k_total=R,
-                    accumulate=accumulate, splits=splits, tiles=tiles,
-                    stages=STAGES["wgrad"] or (t or {}).get("stages", 0),
-                    persist=0 if upd is not None else _persist("wgrad", t), upd=upd, ct=wt)
-    if R % 64 or splits > R // 64:
+    kmajor = dzt is not None and xt is not None and dz.is_cuda
+    if not kmajor and (R % 64 or splits > R // 64):
         raise ValueError("rows must be a multiple of 64 with at least 64 rows per split")
-    bm, bn, s = wgrad_config(N, K, R)
-    tiles = (bm, bn) if s == splits else pick_tiles(N, K, splits)
-    t = tuning.lookup("wgrad", N, K, R) if s == splits else None
-    if upd is None and splits == 1 and dz.is_cuda and \
-            _blas("wgrad", tuning.lookup("wgrad", N, K, R)) and \
+    p = plan("wgrad", N, K, R, splits)
+    if not kmajor and upd is None and splits == 1 and dz.is_cuda and p.blas and \
             _blas_ok(dz, x, slabs[0], True, False, N, K, R, None, False, accumulate):
         return blas_gemm(dz, x, slabs[0], trans_a=True, trans_b=False, M=N, N=K, K=R,
-                         accumulate=accumulate,
-                         algo=(tuning.lookup("wgrad", N, K, R) or {}).get("blas_algo", 0))
-    return gemm(dz, x, slabs, layout_a=MNMAJ, layout_b=MNMAJ, M=N, N=K, K=R, k_total=R,
-                accumulate=accumulate, splits=splits, tiles=tiles,
-                stages=STAGES["wgrad"] or (t or {}).get("stages", 0),
-                persist=0 if upd is not None else _persist("wgrad", t), upd=upd, ct=wt)
+                         accumulate=accumulate, algo=p.blas_algo)
+    a, b, layout = (dzt, xt, KMAJ) if kmajor else (dz, x, MNMAJ)
+    return gemm(a, b, slabs, layout_a=layout, layout_b=layout, M=N, N=K, K=R, k_total=R,
+                accumulate=accumulate, splits=splits, upd=upd, ct=wt,
+                **p.launch_args(upd=upd is not None))
 
 
 def linear_wgrad_group(items) -> list:
@@ -739,13 +515,12 @@ def linear_wgrad_group(items) -> list:
     for idx, (dz, x, slabs, splits, acc) in enumerate(items):
         R, N = dz.shape
         K = x.shape[1]
-        bm, bn, s = wgrad_config(N, K, R)
-        t = tuning.lookup("wgrad", N, K, R)
-        stages = STAGES["wgrad"] or (t or {}).get("stages", 0) or 2
+        p = plan("wgrad", N, K, R)
+        bm, bn = p.tiles
         small = -(-N // bm) * -(-K // bn) * splits < int(
             switches.get("DNN_WGRAD_GROUP_MAX_WG"))  # under one round of the chip
-        if (R % 64 or splits > R // 64 or s != splits or _persist("wgrad", t) or
-                _blas("wgrad", t) or stages != 2 or not small or
+        if (R % 64 or splits > R // 64 or p.splits != splits or p.persist or p.blas or
+                (p.stages or GROUP_STAGES) != GROUP_STAGES or not small or
                 (bm, bn) not in ((64, 64), (64, 128), (128, 64), (128, 128))):
             rest.append(idx)
             continue
@@ -767,7 +542,8 @@ def linear_wgrad_group(items) -> list:
                     raise ValueError("split-K output must be [splits][N][K] fp32")
                 probs.append((_p(dz), dz.stride(0), _p(x), x.stride(0), _p(slabs),
                               slabs.stride(1), slabs.stride(0), N, K, R, R, int(acc), splits))
-            native().gemm_bf16_group(probs, MNMAJ, MNMAJ, 1, bm, bn, 2, _stream(items[0][0]))
+            native().gemm_bf16_group(probs, MNMAJ, MNMAJ, 1, bm, bn, GROUP_STAGES,
+                                     _stream(items[0][0]))
     return sorted(rest)
 
 

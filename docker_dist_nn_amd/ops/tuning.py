@@ -2,7 +2,7 @@
 
 ``tuned_gfx950.json`` maps a GEMM signature to the fastest (tile, split-K, pipeline depth)
 measured on an MI355X by ``bench/tune.py``. The ops consult it first and fall back to the
-analytic rules in :mod:`.kernels` for shapes it does not cover. Lookups are deterministic, so a
+analytic rules in :mod:`.gemm_plan` for shapes it does not cover. Lookups are deterministic, so a
 given shape always runs the same kernel configuration (bitwise-reproducible training).
 
 Signatures (the GEMM as the kernel sees it: C[M][N] = sum over K):

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from docker_dist_nn_amd import ops
-from docker_dist_nn_amd.ops.kernels import FRAG_WAVES
+from docker_dist_nn_amd.ops.gemm_plan import FRAG_WAVES
 
 
 def pack(bits: torch.Tensor, tiles) -> torch.Tensor:

@@ -99,7 +99,7 @@ def test_persist_dgrad_mask_equals_classic(dev, bm, bn, act, wt):
 
 def test_persist_step_ops_env(dev, monkeypatch):
     """The linear_* ops honour DNN_GEMM_PERSIST / the tuned table's "persist" field."""
-    monkeypatch.setitem(ops.kernels.PERSIST, "fwd", 1)
+    monkeypatch.setitem(ops.gemm_plan.PERSIST, "fwd", 1)
     gen = torch.Generator().manual_seed(0)
     x = torch.randn(4096, 832, generator=gen).to(torch.bfloat16).to(dev)
     w = (torch.randn(512, 832, generator=gen) * 0.05).to(torch.bfloat16).to(dev)

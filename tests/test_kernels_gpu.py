@@ -553,7 +553,7 @@ def test_register_prefetch_bitwise(dev, la, lb):
         assert torch.all(blocked[:, 33:, :] == 0xAA)  # chunks past N/8 untouched
         assert torch.equal(ops.relu_mask_bits(mn, M, N), cn > 0)
         # fragment-order masks (ld_mask < 0): same outputs, one wide access per lane
-        if (bm, bn) in ops.kernels.FRAG_WAVES:
+        if (bm, bn) in ops.gemm_plan.FRAG_WAVES:
             fm = ops.FragMask.alloc(M, N, (bm, bn), dev)
             cf = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
             ops.gemm(a, b, cf, layout_a=la, layout_b=lb, M=M, N=N, K=K, bias=bias, act="relu",

@@ -4,6 +4,7 @@ flags, and the DNN_BLAS parser."""
 import torch
 
 from docker_dist_nn_amd import ops
+from docker_dist_nn_amd.ops import gemm_plan as P
 from docker_dist_nn_amd.ops import kernels as K
 from docker_dist_nn_amd.ops import reference as ref
 
@@ -60,14 +61,14 @@ def test_build_reads_per_file_flags():
 
 def test_blas_switch(monkeypatch):
     monkeypatch.delenv("DNN_BLAS", raising=False)
-    assert K._blas_requested("fwd", {"blas": 1}) and not K._blas_requested("fwd", {"tile": [64, 64]})
-    assert not K._blas_requested("fwd", None)
+    assert P._blas_requested("fwd", {"blas": 1}) and not P._blas_requested("fwd", {"tile": [64, 64]})
+    assert not P._blas_requested("fwd", None)
     monkeypatch.setenv("DNN_BLAS", "0")
-    assert not K._blas_requested("fwd", {"blas": 1})
+    assert not P._blas_requested("fwd", {"blas": 1})
     monkeypatch.setenv("DNN_BLAS", "1")
-    assert K._blas_requested("wgrad", None)
+    assert P._blas_requested("wgrad", None)
     monkeypatch.setenv("DNN_BLAS", "fwd=1,wgrad=0")
-    assert K._blas_requested("fwd", None) and not K._blas_requested("wgrad", {"blas": 1}) and not K._blas_requested("dgrad", None)
+    assert P._blas_requested("fwd", None) and not P._blas_requested("wgrad", {"blas": 1}) and not P._blas_requested("dgrad", None)
 
 
 def test_reference_tail_waves_match_kernel_forms():
