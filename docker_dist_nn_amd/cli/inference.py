@@ -41,6 +41,8 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--local", type=str, default=None,
                     help="model config JSON: run the MI355X engine in-process, no server")
     ap.add_argument("--device", default="auto")
+    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
+                    help="with --local: the engine's weight format")
     ap.add_argument("--metrics-json", type=str, default=None)
     return ap
 
@@ -80,7 +82,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
         mc = load_model_config(a.local)
         dev = torch.device("cpu") if a.device == "cpu" or not torch.cuda.is_available() \
             else torch.device("cuda", 0)
-        eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim)
+        eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
+                              weights=a.weights)
 
         def call(batch):
             return eng.predict(batch)

@@ -12,6 +12,9 @@ stage is a slice of layers on one GPU:
   runs the row-softmax kernel; the last layer writes fp32 outputs;
 * requests are padded to a row bucket (multiple of 64) and, per bucket, the whole forward is
   captured once in a HIP graph, so a batch-1 request is a single graph launch.
+
+``weights="fp8"`` holds the weights as OCP e4m3 codes plus one fp32 scale per output neuron
+(the format of ``ops.quant_rows_fp8``) instead of bf16: see :class:`InferenceStage`.
 """
 from __future__ import annotations
 
@@ -29,10 +32,33 @@ from ..utils.native import native
 from .. import switches
 
 
+WEIGHT_FORMATS = ("bf16", "fp8")
+
+
 class InferenceStage:
+    """A slice of layers on one device.
+
+    ``weights="bf16"`` (the default) keeps each padded weight in bf16 (``self.w``).
+
+    ``weights="fp8"`` quantises each padded bf16 weight once with ``ops.quant_rows_fp8`` -- a
+    weight row is one output neuron -- into ``self.q[i]`` (uint8 [Np][Kp], OCP e4m3 codes) and
+    ``self.s[i]`` (fp32 [Np], row amax / 448) and does not keep the bf16 copy (``self.w`` is
+    empty): one byte per weight resident. Requests of <= 8 rows run ``ops.gemv_fp8``, which
+    streams the codes and applies the scale once per output. Larger buckets dequantise the
+    layer (``ops.dequant_rows_fp8``) into one bf16 scratch buffer sized to the stage's largest
+    layer and run the bf16 GEMM on it; the scratch is reused in stream order, so it is safe
+    under graph and native replay. That path rounds dec * scale to bf16 (at most 2^-9 relative
+    per weight, far below the format's own 2^-4) and moves about 2.5 times the weight bytes of
+    bf16 serving (read 1, write 2, read 2 per weight, against 2): fp8 weights are a
+    small-batch and footprint feature, not a large-batch one.
+    """
+
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
                  expected_input: int, name: str = "layer", is_last: bool = True,
-                 case_sensitive: bool = True):
+                 case_sensitive: bool = True, weights: str = "bf16"):
+        if weights not in WEIGHT_FORMATS:
+            raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
+        self.weights = weights
         self.device = device
         self.name = name
         self.is_last = is_last
@@ -42,13 +68,23 @@ class InferenceStage:
         self.dims = [L.in_dim for L in self.layers] + [self.layers[-1].out_dim]
         self.pads = [round_up(d, 64) for d in self.dims]
         self.w, self.b = [], []
+        self.q, self.s = [], []  # fp8: codes and row scales
         for L, kp, np_ in zip(self.layers, self.pads, self.pads[1:]):
             w = torch.zeros(np_, kp, dtype=torch.float32)
             w[:L.out_dim, :L.in_dim] = torch.as_tensor(np.asarray(L.weight, np.float32))
             b = torch.zeros(np_, dtype=torch.float32)
             b[:L.out_dim] = torch.as_tensor(np.asarray(L.bias, np.float32))
-            self.w.append(w.to(device=device, dtype=torch.bfloat16))
+            w = w.to(device=device, dtype=torch.bfloat16)
+            if weights == "fp8":
+                q = torch.empty(np_, kp, dtype=torch.uint8, device=device)
+                s = torch.empty(np_, dtype=torch.float32, device=device)
+                ops.quant_rows_fp8(w, q, s)
+                self.q.append(q)
+                self.s.append(s)
+            else:
+                self.w.append(w)
             self.b.append(b.to(device))
+        self._wscratch: Optional[torch.Tensor] = None  # fp8, buckets > 8 rows: one bf16 layer
         self._bufs: dict[int, dict] = {}
 
     @property
@@ -86,6 +122,21 @@ class InferenceStage:
             self._bufs[rows] = b
         return b
 
+    def _linear(self, i: int, x: torch.Tensor, y: torch.Tensor, act: str) -> None:
+        """y = act(x . W_i^T + b_i) from the stage's weight format."""
+        if self.weights == "bf16":
+            ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
+        elif x.shape[0] <= ops.GEMV_MAX_ROWS:
+            ops.gemv_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
+        else:
+            if self._wscratch is None:  # (first run of a bucket is eager: never under capture)
+                self._wscratch = torch.empty(max(q.numel() for q in self.q),
+                                             dtype=torch.bfloat16, device=self.device)
+            q = self.q[i]
+            w = self._wscratch[:q.numel()].view(q.shape)
+            ops.dequant_rows_fp8(q, self.s[i], w)
+            ops.linear_fwd(x, w, self.b[i], y, act=act)
+
     def forward(self, rows: int, x: Optional[torch.Tensor] = None,
                 upto: Optional[int] = None) -> torch.Tensor:
         """Run on buffers(rows)['x'] (or on ``x``, e.g. the device-side chain's input rows);
@@ -100,17 +151,17 @@ class InferenceStage:
             last = i == n - 1
             h, f = b["h"][i], b["f32"][i]
             if act == "softmax":
-                ops.linear_fwd(x, self.w[i], self.b[i], f, act="linear")
+                self._linear(i, x, f, "linear")
                 ops.softmax_rows(f, f, self.dims[i + 1])
                 if last and self.is_last:
                     return f
                 ops.pack_bf16(f[:, :self.dims[i + 1]], h)
                 x = h
             elif last and self.is_last:
-                ops.linear_fwd(x, self.w[i], self.b[i], f, act=act)
+                self._linear(i, x, f, act)
                 return f
             else:
-                ops.linear_fwd(x, self.w[i], self.b[i], h, act=act)
+                self._linear(i, x, h, act)
                 x = h
         return x
 
@@ -120,14 +171,15 @@ class InferenceEngine:
 
     def __init__(self, stage_layers: Sequence[Sequence[LayerWeights]], device: torch.device,
                  expected_input: int, names: Optional[Sequence[str]] = None,
-                 max_rows: int = 65536, use_graphs: bool = True):
+                 max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16"):
+        """``weights``: "bf16" or "fp8" (see :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
         names = list(names or [f"layer_container_{i}" for i in range(len(stage_layers))])
         for i, ls in enumerate(stage_layers):
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
-                                is_last=i == len(stage_layers) - 1)
+                                is_last=i == len(stage_layers) - 1, weights=weights)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

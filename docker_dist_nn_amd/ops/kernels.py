@@ -443,6 +443,32 @@ def dequant_rows_fp8(q, scale, x):
                               _stream(x))
 
 
+def gemv_fp8(x, q, scale, bias, y, act="relu"):
+    """Serving-size layer (1..8 rows) over fp8 weight rows in the format of quant_rows_fp8:
+    y[m][n] = act(fl32(scale[n] * sum_k x[m][k] * e4m3(q[n][k])) + bias[n]), one wave per output
+    neuron, the scale applied once to the reduced sum (csrc/kernels/gemv_fp8.hip). x bf16
+    [M][K], q uint8 [N][>=K] e4m3 codes, scale fp32 [>=N], y bf16 or fp32; K % 16 == 0."""
+    M, K = x.shape
+    N = q.shape[0]
+    if M > GEMV_MAX_ROWS or K % 16:
+        raise ValueError(f"gemv_fp8 takes <= {GEMV_MAX_ROWS} rows and K % 16 == 0")
+    _rows(x, "x", torch.bfloat16)
+    _rows(q, "q", torch.uint8)
+    if q.shape[1] < K or y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("gemv_fp8 operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if scale.dtype != torch.float32 or scale.numel() < N or not scale.is_contiguous():
+        raise ValueError("scale must be contiguous fp32 with >= N entries")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not x.is_cuda:
+        return ref.gemv_fp8(x, q, scale, bias, y, M, N, K, _act(act))
+    native().gemv_fp8(_p(x), x.stride(0), _p(q), q.stride(0), _p(scale), _p(bias), _p(y),
+                      y.stride(0), M, N, K, _act(act), int(y.dtype == torch.float32), _stream(x))
+    return y
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

@@ -73,6 +73,30 @@ def gemm(a, b, c, *, layout_a, layout_b, M, N, K, bias=None, aux=None, act=0, ac
     return c
 
 
+def e4m3_table() -> torch.Tensor:
+    """fp64 value of each of the 256 OCP e4m3 codes, from the bit fields (1 sign, 4 exponent
+    bits with bias 7, 3 mantissa bits, subnormals at exponent 0, 0x7F / 0xFF = NaN)."""
+    c = torch.arange(256)
+    s, e, m = c >> 7, (c >> 3) & 15, (c & 7).double()
+    v = torch.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * torch.pow(2.0, (e - 7).double()))
+    v = torch.where((e == 15) & (m == 7), torch.full_like(v, float("nan")), v)
+    return torch.where(s == 1, -v, v)
+
+
+_E4M3 = e4m3_table()
+
+
+def gemv_fp8(x, q, scale, bias, y, M, N, K, act):
+    """y[:M, :N] = act(fl32(scale * fl32(S)) + bias), S = x . dec(q)^T in fp64: the sum of the
+    kernel without its summation error, then the kernel's fp32 epilogue."""
+    S = x[:M, :K].double() @ _E4M3[q[:N, :K].long()].t()
+    v = scale[:N].float() * S.float()
+    if bias is not None:
+        v = v + bias[:N].float()
+    y[:M, :N] = act_fwd(v, act).to(y.dtype)
+    return y
+
+
 def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
                  rows_per_block=64, colsum=None):
     rows, width = dz.shape

@@ -451,11 +451,14 @@ def main(argv: Optional[list[str]] = None) -> int:
     layers = load_model_config(st["neurons_file"]).layers
     names = [s["name"] for s in plan["stages"]]
     stage = InferenceStage(layers, device, expected_input=st["expected_input"], name=st["name"],
-                           is_last=rank == world - 1)
+                           is_last=rank == world - 1, weights=plan.get("weights", "bf16"))
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))
     if world > 1 and use_gpu and switches.get("DNN_CHAIN_FAST") == "1":
-        why = cr.enable_fast()
+        if stage.weights == "fp8":  # the device-side chain reads bf16 weights (stage.w)
+            why = "fp8 weights (host chain)"
+        else:
+            why = cr.enable_fast()
         if rank == 0:
             log.info(f"({st['name']}) serving-size requests: {why}")
     log.info(f"({st['name']}) stage ready on {device}: {len(layers)} layer(s), "

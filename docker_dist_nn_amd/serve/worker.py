@@ -10,6 +10,9 @@ The reference runs one container per stage whose behaviour is fixed by environme
   NEURONS_CONFIG      the stage's {"layer_1": [neurons...], ...} JSON inline, or
   NEURONS_FILE_CONFIG a path to it (the launcher's choice for configs > 1000 characters)
 
+and one entry of this project's: STAGE_WEIGHTS, "bf16" (default) or "fp8", the weight format
+of the stage's engine (run_grpc_fcnn.py --weights).
+
 This worker keeps that contract, the LayerService protocol and the error mapping of
 grpc_node.py:99-158 (ValueError -> INVALID_ARGUMENT, a failed forward keeps the downstream
 code and reports "Failed to forward request to <host:port>: <details>", anything else ->
@@ -71,7 +74,8 @@ class StageWorker:
             dev = torch.device("cuda", int(env.get("LOCAL_RANK", "0")) % max(1, n))
             torch.cuda.set_device(dev)
         return InferenceEngine([self.layers], dev, expected_input=self.expected_input_dim,
-                               names=[self.container_name])
+                               names=[self.container_name],
+                               weights=env.get("STAGE_WEIGHTS", "bf16") or "bf16")
 
     def _client(self):
         from .ingress import LayerClient
