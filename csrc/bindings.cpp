@@ -22,6 +22,7 @@
 #include "kernels/gemm.hpp"
 #include "kernels/gemv.hpp"
 #include "kernels/gemv_fp8.hpp"
+#include "kernels/linear_fp8.hpp"
 #include "kernels/mlp_tail.hpp"
 #include "runtime/blaslt.hpp"
 #include "runtime/chain_host.hpp"
@@ -197,6 +198,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("ldq"), py::arg("scale"),
       py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("act"), py::arg("out_f32"), py::arg("stream"));
+  m.def(
+      "linear_fp8",
+      [](uintptr_t x, long ldx, uintptr_t q, long ldq, uintptr_t scale, uintptr_t bias,
+         uintptr_t y, long ldy, int M, int N, int K, int act, int out_f32, uintptr_t stream,
+         int tile) {
+        launch(
+            "linear_fp8",
+            [=](hipStream_t s, const dnn::Program& R) {
+              return dnn::linear_fp8(R.fix(P<const uint16_t>(x)), ldx,
+                                     R.fix(P<const unsigned char>(q)), ldq,
+                                     R.fix(P<const float>(scale)), R.fix(P<const float>(bias)),
+                                     R.fix(P<void>(y)), ldy, M, N, K, act, out_f32, tile, s);
+            },
+            stream);
+      },
+      py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("ldq"), py::arg("scale"),
+      py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
+      py::arg("act"), py::arg("out_f32"), py::arg("stream"), py::arg("tile") = 0);
   m.def(
       "gemm_bf16_streamk",
       [](uintptr_t a, long lda, uintptr_t b, long ldb, uintptr_t c, long ldc, int M, int N, int K,

@@ -49,6 +49,10 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="serving weight format: fp8 = e4m3 codes + one scale per output neuron "
                          "(half the resident bytes; requests of <= 8 rows stream them directly)")
+    ap.add_argument("--fp8-gemm", choices=["scratch", "direct"], default="scratch",
+                    help="with --weights fp8, buckets of more than 8 rows: scratch = dequantise "
+                         "the layer into a bf16 buffer + the bf16 GEMM; direct = the fp8-weight "
+                         "GEMM on the codes, up to ops.FP8_DIRECT_MAX_ROWS rows")
     ap.add_argument("--port", type=int, default=5101)
     ap.add_argument("--layer-distribution", type=str, default=None,
                     help="override, e.g. '[1,1,1]'")
@@ -270,7 +274,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             dev = _device(a.device)
             eng = InferenceEngine([mc.layers[p.layer_start:p.layer_end] for p in plans], dev,
                                   expected_input=input_dim, names=[s["name"] for s in stage_entries],
-                                  weights=a.weights)
+                                  weights=a.weights, fp8_gemm=a.fp8_gemm)
             server = serve(eng.predict, port=a.port, name=stage_entries[0]["name"])
         elif mode == "workers":
             from ..launch import spawn_workers, wait_for_port
@@ -293,6 +297,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                 e["DNN_HOP_TIMEOUT"] = str(a.hop_timeout)
                 e["DNN_WORKER_DEVICE"] = "cpu" if a.device == "cpu" else "auto"
                 e["STAGE_WEIGHTS"] = a.weights
+                e["STAGE_FP8_GEMM"] = a.fp8_gemm
                 e["LOCAL_RANK"] = str(k)
                 stage_envs.append(e)
             job = spawn_workers("docker_dist_nn_amd.serve.worker", stage_envs,
@@ -308,7 +313,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             plan_path = os.path.join(a.cache_dir, "chain_plan.json")
             json.dump({"stages": stage_entries, "port": a.port, "hop_timeout": a.hop_timeout,
                        "device": "cpu" if a.device == "cpu" else "auto",
-                       "weights": a.weights}, open(plan_path, "w"))
+                       "weights": a.weights, "fp8_gemm": a.fp8_gemm}, open(plan_path, "w"))
             job = spawn_ranks("docker_dist_nn_amd.serve.chain", ["--plan", plan_path], n_st,
                               devices=list(range(n_st)) if a.device != "cpu" else None,
                               names=[s["name"] for s in stage_entries])

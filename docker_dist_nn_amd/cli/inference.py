@@ -43,6 +43,9 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--device", default="auto")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="with --local: the engine's weight format")
+    ap.add_argument("--fp8-gemm", choices=["scratch", "direct"], default="scratch",
+                    help="with --local --weights fp8: how buckets of more than 8 rows run "
+                         "(InferenceStage)")
     ap.add_argument("--metrics-json", type=str, default=None)
     return ap
 
@@ -83,7 +86,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
         dev = torch.device("cpu") if a.device == "cpu" or not torch.cuda.is_available() \
             else torch.device("cuda", 0)
         eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
-                              weights=a.weights)
+                              weights=a.weights, fp8_gemm=a.fp8_gemm)
 
         def call(batch):
             return eng.predict(batch)

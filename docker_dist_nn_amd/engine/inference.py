@@ -33,6 +33,7 @@ from .. import switches
 
 
 WEIGHT_FORMATS = ("bf16", "fp8")
+FP8_GEMMS = ("scratch", "direct")
 
 
 class InferenceStage:
@@ -49,16 +50,27 @@ class InferenceStage:
     layer and run the bf16 GEMM on it; the scratch is reused in stream order, so it is safe
     under graph and native replay. That path rounds dec * scale to bf16 (at most 2^-9 relative
     per weight, far below the format's own 2^-4) and moves about 2.5 times the weight bytes of
-    bf16 serving (read 1, write 2, read 2 per weight, against 2): fp8 weights are a
-    small-batch and footprint feature, not a large-batch one.
+    bf16 serving (read 1, write 2, read 2 per weight, against 2).
+
+    ``fp8_gemm="direct"`` (with ``weights="fp8"``; ignored with bf16) runs the buckets of
+    9 .. ``ops.FP8_DIRECT_MAX_ROWS`` rows on ``ops.linear_fwd_fp8`` instead: the MFMA kernel
+    takes the codes as its weight operand and applies the scale once per output, exactly as the
+    <= 8-row path does, so the format means the same on both sides of the 8/9-row line and no
+    bf16 copy of a layer is written (such a bucket never allocates the scratch). Larger buckets
+    keep the scratch path: at thousands of rows the GEMM is compute-bound and the detour is
+    amortised. ``"scratch"`` (the default) is the path above for every bucket over 8 rows.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
                  expected_input: int, name: str = "layer", is_last: bool = True,
-                 case_sensitive: bool = True, weights: str = "bf16"):
+                 case_sensitive: bool = True, weights: str = "bf16",
+                 fp8_gemm: str = "scratch"):
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
+        if fp8_gemm not in FP8_GEMMS:
+            raise ValueError(f"fp8_gemm must be one of {FP8_GEMMS}, got {fp8_gemm!r}")
         self.weights = weights
+        self.fp8_gemm = fp8_gemm
         self.device = device
         self.name = name
         self.is_last = is_last
@@ -128,6 +140,8 @@ class InferenceStage:
             ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
         elif x.shape[0] <= ops.GEMV_MAX_ROWS:
             ops.gemv_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
+        elif self.fp8_gemm == "direct" and x.shape[0] <= ops.FP8_DIRECT_MAX_ROWS:
+            ops.linear_fwd_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
         else:
             if self._wscratch is None:  # (first run of a bucket is eager: never under capture)
                 self._wscratch = torch.empty(max(q.numel() for q in self.q),
@@ -171,15 +185,18 @@ class InferenceEngine:
 
     def __init__(self, stage_layers: Sequence[Sequence[LayerWeights]], device: torch.device,
                  expected_input: int, names: Optional[Sequence[str]] = None,
-                 max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16"):
-        """``weights``: "bf16" or "fp8" (see :class:`InferenceStage`), for every stage."""
+                 max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
+                 fp8_gemm: str = "scratch"):
+        """``weights``: "bf16" or "fp8", ``fp8_gemm``: "scratch" or "direct" (see
+        :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
         names = list(names or [f"layer_container_{i}" for i in range(len(stage_layers))])
         for i, ls in enumerate(stage_layers):
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
-                                is_last=i == len(stage_layers) - 1, weights=weights)
+                                is_last=i == len(stage_layers) - 1, weights=weights,
+                                fp8_gemm=fp8_gemm)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

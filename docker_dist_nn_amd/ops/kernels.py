@@ -469,6 +469,47 @@ def gemv_fp8(x, q, scale, bias, y, act="relu"):
     return y
 
 
+# Largest row bucket the serving engine runs on linear_fwd_fp8 under fp8_gemm="direct"; larger
+# buckets keep the dequantise-into-scratch path. Measured (bench/linear_fp8_bench.py,
+# profiles/linear_fp8/linear_fp8_bench.jsonl): the largest power-of-two bucket at which direct
+# beats scratch on both layers (1024 x 1024 resident, 8192 x 8192 cold) by more than the larger
+# of the two spreads. 1024 is also the largest bucket measured: 7.8 vs 14.4 us and 165.7 vs
+# 170.2 us (spreads <= 1 %); the margin on the large layer is 3 % there, so nothing above it
+# is claimed.
+FP8_DIRECT_MAX_ROWS = 1024
+
+
+def linear_fwd_fp8(x, q, scale, bias, y, act="relu", tile=0):
+    """Forward layer over fp8 weight rows in the format of quant_rows_fp8, any number of rows:
+    y[m][n] = act(fl32(scale[n] * sum_k x[m][k] * e4m3(q[n][k])) + bias[n]) -- gemv_fp8's
+    definition. Up to GEMV_MAX_ROWS rows run gemv_fp8; more rows run the MFMA kernel that takes
+    the codes as its weight operand (csrc/kernels/linear_fp8.hip; no bf16 copy of the weights).
+    x bf16 [M][K], q uint8 [N][>=K] e4m3 codes, scale fp32 [>=N], y bf16 or fp32; K % 16 == 0.
+    ``tile``: 0 = chosen by the launcher, 1..4 force one (linear_fp8.hpp; tests, benchmark)."""
+    M, K = x.shape
+    N = q.shape[0]
+    if K % 16:
+        raise ValueError("linear_fwd_fp8 takes K % 16 == 0")
+    _rows(x, "x", torch.bfloat16)
+    _rows(q, "q", torch.uint8)
+    if q.shape[1] < K or y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("linear_fwd_fp8 operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if scale.dtype != torch.float32 or scale.numel() < N or not scale.is_contiguous():
+        raise ValueError("scale must be contiguous fp32 with >= N entries")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not x.is_cuda:
+        return ref.gemv_fp8(x, q, scale, bias, y, M, N, K, _act(act))
+    if M <= GEMV_MAX_ROWS and not tile:
+        return gemv_fp8(x, q, scale, bias, y, act)
+    native().linear_fp8(_p(x), x.stride(0), _p(q), q.stride(0), _p(scale), _p(bias), _p(y),
+                        y.stride(0), M, N, K, _act(act), int(y.dtype == torch.float32),
+                        _stream(x), tile)
+    return y
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

@@ -10,8 +10,9 @@ The reference runs one container per stage whose behaviour is fixed by environme
   NEURONS_CONFIG      the stage's {"layer_1": [neurons...], ...} JSON inline, or
   NEURONS_FILE_CONFIG a path to it (the launcher's choice for configs > 1000 characters)
 
-and one entry of this project's: STAGE_WEIGHTS, "bf16" (default) or "fp8", the weight format
-of the stage's engine (run_grpc_fcnn.py --weights).
+and two entries of this project's: STAGE_WEIGHTS, "bf16" (default) or "fp8", the weight format
+of the stage's engine (run_grpc_fcnn.py --weights), and STAGE_FP8_GEMM, "scratch" (default) or
+"direct", how an fp8 stage runs buckets of more than 8 rows (--fp8-gemm).
 
 This worker keeps that contract, the LayerService protocol and the error mapping of
 grpc_node.py:99-158 (ValueError -> INVALID_ARGUMENT, a failed forward keeps the downstream
@@ -75,7 +76,8 @@ class StageWorker:
             torch.cuda.set_device(dev)
         return InferenceEngine([self.layers], dev, expected_input=self.expected_input_dim,
                                names=[self.container_name],
-                               weights=env.get("STAGE_WEIGHTS", "bf16") or "bf16")
+                               weights=env.get("STAGE_WEIGHTS", "bf16") or "bf16",
+                               fp8_gemm=env.get("STAGE_FP8_GEMM", "scratch") or "scratch")
 
     def _client(self):
         from .ingress import LayerClient
