@@ -7,7 +7,11 @@ With fewer GPUs than stages (the one-GPU pool) every stage runs on cuda:0 and th
 through host memory over gloo (``rehearsal``: DNN_FORCE_DEVICE=0, DNN_DIST_BACKEND=gloo); on an
 8-GPU node each stage has its own GPU and the hops are RCCL. One JSON line.
 
-Usage: python bench/chain_latency.py [--iters 500] [--rows 1] [--stages 8]"""
+``--weights fp8`` serves from e4m3 weight codes (run_grpc_fcnn.py --weights): on the device-side
+chain by default, on the host chain with DNN_CHAIN_FAST=0 in the environment.
+
+Usage: python bench/chain_latency.py [--iters 500] [--rows 1] [--stages 8] [--width 1024]
+                                     [--weights {bf16,fp8}]"""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +34,8 @@ def main():
     ap.add_argument("--rows", type=int, default=1)
     ap.add_argument("--stages", type=int, default=8)
     ap.add_argument("--width", type=int, default=1024)
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
+                    help="the stages' resident weight format (run_grpc_fcnn.py --weights)")
     ap.add_argument("--log", default=None, help="write the servers' log here")
     a = ap.parse_args()
     import torch
@@ -64,7 +70,8 @@ def main():
         p = subprocess.Popen([sys.executable, os.path.join(ROOT, "src", "run_grpc_fcnn.py"),
                               "--config", cfg, "--inputs", inp, "--port", str(port),
                               "--mode", "ranks", "--device", "cuda" if n_gpu else "cpu",
-                              "--cache-dir", os.path.join(d, "cache"), "--run-for", "600"],
+                              "--cache-dir", os.path.join(d, "cache"), "--run-for", "600",
+                              "--weights", a.weights],
                              env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         ok = True
         try:
@@ -100,13 +107,15 @@ def main():
                 print((log or "")[-6000:], file=sys.stderr, flush=True)
     fast = "device-side chain" in (log or "")
     import re
-    m = re.search(r"predict latency over (\d+) requests: p50 ([\d.]+) ms p90 ([\d.]+) ms "
-                  r"p99 ([\d.]+) ms", log or "")
-    inner = ({"requests": int(m.group(1)), "p50_ms": float(m.group(2)),
-              "p90_ms": float(m.group(3)), "p99_ms": float(m.group(4))} if m else None)
+    m = re.search(r"(device-side|message) chain predict latency over (\d+) requests: "
+                  r"p50 ([\d.]+) ms p90 ([\d.]+) ms p99 ([\d.]+) ms", log or "")
+    inner = ({"path": m.group(1) + " chain", "requests": int(m.group(2)),
+              "p50_ms": float(m.group(3)), "p90_ms": float(m.group(4)),
+              "p99_ms": float(m.group(5))} if m else None)
     t = np.asarray(ts) * 1e3
     print(json.dumps({"metric": "inference chain latency", "path": "rank chain (grpc ingress)",
                       "stages": a.stages, "rows": a.rows, "model": "-".join(map(str, dims)),
+                      "weights": a.weights,
                       "transport": ("device-side chain: IPC slots + flags (serve/fastpath.py)"
                                     if fast else "gloo via host" if rehearsal else "rccl") +
                                    (", one-GPU rehearsal: every stage on cuda:0"
@@ -114,7 +123,8 @@ def main():
                       "gpu_max_hw_queues": env.get("GPU_MAX_HW_QUEUES"),
                       "persistent_stages": env.get("DNN_CHAIN_PERSIST", "1") == "1",
                       # rank 0's predict() alone (request in -> logits out, no gRPC): the
-                      # device-side chain's own latency, warm-up requests included
+                      # chain's own latency (device-side, or the message chain where that is
+                      # what served), warm-up requests included
                       "chain_only": inner,
                       "p50_ms": round(float(np.percentile(t, 50)), 4),
                       "p90_ms": round(float(np.percentile(t, 90)), 4),

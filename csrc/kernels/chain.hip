@@ -2,6 +2,23 @@
 // single lane polling a flag with system-scope acquire loads and s_sleep between polls, with a
 // wall-clock timeout, so every wave of every launch finishes. Flags and slot headers are
 // written with vector stores (the address is lane-indexed), never through the scalar cache.
+//
+// Weight rows are bf16, or (w_scale != nullptr) OCP e4m3 codes with one fp32 scale per output
+// neuron, summed in gemv_fp8.hip's order so the rows are bitwise that kernel's. Registers of the
+// fp8 forms (hipcc -O3 for gfx950, kernel-resource-usage remark; none has scratch; the bf16
+// forms are what they were: 56 / 92 / 158 / 255 and 253 VGPRs):
+//   kernel                          rows capacity   NB   U   VGPRs   waves/SIMD
+//   chain_gemv_send_kernel<.,.,1>         1          1   4     76        6
+//                                         2          1   4    124        4
+//                                         4          1   2    122        4
+//                                         8          1   2    202        2
+//   chain_stage_kernel<true>              1          4   4    242        2
+//   (one kernel holds all four            2          4   4   (the whole kernel)
+//   cs_layer_fp8 forms)                   4          4   2
+//                                         8          4   2
+// (NB: neurons a wave holds at once; U: 1024-column chunks whose loads are in flight together.
+// The stage kernel reads x from LDS 8 columns at a time: with a lane's 16 columns of 8 rows
+// held at once it needed 256 VGPRs + 20 AGPRs and ran at 1 wave/SIMD.)
 #include <algorithm>
 
 #include "chain.hpp"
@@ -131,7 +148,65 @@ __device__ __forceinline__ uint32_t hop_status(uint32_t status, const uint32_t* 
 
 constexpr int CG_WAVES = 4;  // output neurons (waves) per 256-thread workgroup, as gemv.hip
 
-template <int M, bool OUT_F32>
+// ---- fp8 weight rows (w_scale != nullptr) ----------------------------------------------------
+// gemv_fp8.hip's sum, bit for bit: lane l owns columns k0 + 1024 u + 16 l .. + 15 of every
+// 1024-column chunk, chunks ascending, columns ascending, then wave_sum; dec * x is exact in
+// fp32, so only this order fixes the result (not U, not how many neurons a wave holds).
+constexpr int C8_CHUNK = 1024;  // columns per chunk: 64 lanes x 16 codes
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+// acc[m] += sum over 8 of the lane's columns (two words of codes) of dec(code) * x[m][column],
+// columns ascending
+template <int M>
+__device__ __forceinline__ void fp8_fma8(unsigned w0, unsigned w1, const bf16x8_t (&xv)[M],
+                                         float (&acc)[M]) {
+  const unsigned word[2] = {w0, w1};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {  // word j holds columns 4 j .. 4 j + 3
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(word[j], false);
+    const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(word[j], true);
+    const float we[4] = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[m] += we[c] * bf2f((u16)xv[m][4 * j + c]);
+    }
+  }
+}
+
+// One neuron's fp8 row against `rows` <= M input rows in global memory (chain_gemv_send; the
+// loop of gemv_fp8_kernel: all loads of U chunks are issued before any is used).
+template <int M, int U>
+__device__ __forceinline__ void fp8_row_sum(const unsigned char* qr, const u16* x, long ldx,
+                                            int rows, int K, int lane, float (&acc)[M]) {
+  for (int k0 = 0; k0 < K; k0 += C8_CHUNK * U) {
+    uint4 qv[U];
+    bf16x8_t xv[U][2][M];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = k0 + u * C8_CHUNK + lane * 16;
+      if (k < K) {  // K % 16 == 0: a lane's 16 columns are inside K or wholly outside
+        qv[u] = *(const uint4*)(qr + k);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          xv[u][0][m] = m < rows ? *(const bf16x8_t*)(x + m * ldx + k) : bf16x8_t{};
+          xv[u][1][m] = m < rows ? *(const bf16x8_t*)(x + m * ldx + k + 8) : bf16x8_t{};
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (k0 + u * C8_CHUNK + lane * 16 < K) {
+        fp8_fma8<M>(qv[u].x, qv[u].y, xv[u][0], acc);
+        fp8_fma8<M>(qv[u].z, qv[u].w, xv[u][1], acc);
+      }
+  }
+}
+
+// FP8: p.w holds e4m3 codes and p.w_scale their row scales; only the k loop and the scale
+// multiply differ -- the waits, hop_status, counter, header, flag and ack are the bf16 form's.
+// Registers: the file header; U as gemv_fp8.hip (8 rows at U = 4 cannot be held).
+template <int M, bool OUT_F32, bool FP8 = false>
 __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
   __shared__ uint32_t s_go;
   const unsigned t = threadIdx.x;
@@ -156,32 +231,37 @@ __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
   // workgroup spins, so the grid is capped) a wave takes every (grid * 4)-th neuron
   for (int n = blockIdx.x * CG_WAVES + (int)(t >> 6); s_go && n < p.N;
        n += gridDim.x * CG_WAVES) {  // (no early return: every thread reaches the barrier)
-    const uint16_t* wr = p.w + (long)n * p.ldw;
     float acc[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[m] = 0.f;
-    constexpr int U = 4;
-    for (int k0 = 0; k0 < p.K; k0 += 512 * U) {
-      bf16x8_t wv[U], xv[U][M];
+    if constexpr (FP8) {
+      fp8_row_sum<M, (M <= 2 ? 4 : 2)>((const unsigned char*)p.w + (long)n * p.ldw, p.x, p.ldx,
+                                       p.rows, p.K, lane, acc);
+    } else {
+      const uint16_t* wr = p.w + (long)n * p.ldw;
+      constexpr int U = 4;
+      for (int k0 = 0; k0 < p.K; k0 += 512 * U) {
+        bf16x8_t wv[U], xv[U][M];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = k0 + u * 512 + lane * 8;
-        if (k < p.K) {
-          wv[u] = *(const bf16x8_t*)(wr + k);
+        for (int u = 0; u < U; ++u) {
+          const int k = k0 + u * 512 + lane * 8;
+          if (k < p.K) {
+            wv[u] = *(const bf16x8_t*)(wr + k);
 #pragma unroll
-          for (int m = 0; m < M; ++m)
-            xv[u][m] = m < p.rows ? *(const bf16x8_t*)(p.x + m * p.ldx + k) : bf16x8_t{};
+            for (int m = 0; m < M; ++m)
+              xv[u][m] = m < p.rows ? *(const bf16x8_t*)(p.x + m * p.ldx + k) : bf16x8_t{};
+          }
         }
-      }
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = k0 + u * 512 + lane * 8;
-        if (k < p.K) {
+        for (int u = 0; u < U; ++u) {
+          const int k = k0 + u * 512 + lane * 8;
+          if (k < p.K) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float we = bf2f((u16)wv[u][e]);
+            for (int e = 0; e < 8; ++e) {
+              const float we = bf2f((u16)wv[u][e]);
 #pragma unroll
-            for (int m = 0; m < M; ++m) acc[m] += we * bf2f((u16)xv[u][m][e]);
+              for (int m = 0; m < M; ++m) acc[m] += we * bf2f((u16)xv[u][m][e]);
+            }
           }
         }
       }
@@ -193,7 +273,13 @@ __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
 #pragma unroll
       for (int m = 0; m < M; ++m)
         if (m == lane) v = acc[m];
-      v = act_fwd(v + (p.bias ? p.bias[n] : 0.f), p.act);
+      if constexpr (FP8) {  // gemv_fp8_kernel's epilogue, statement for statement
+        v = __fmul_rn(p.w_scale[n], v);
+        v += p.bias ? p.bias[n] : 0.f;
+        v = act_fwd(v, p.act);
+      } else {
+        v = act_fwd(v + (p.bias ? p.bias[n] : 0.f), p.act);
+      }
       if constexpr (OUT_F32)
         ((float*)p.dst)[(long)lane * p.dst_ld + n] = v;
       else
@@ -301,8 +387,84 @@ __device__ __forceinline__ void cs_layer(const ChainStage& p, const u16* xs, int
   }
 }
 
-constexpr int CS_NB = 4;  // neurons per wave in flight (chain_stage_kernel)
+// cs_layer over fp8 weight rows (p.w_scale != nullptr): per neuron fp8_row_sum's order, so the
+// outputs are bitwise gemv_fp8.hip's. A lane's 16 codes of each of the NB neurons are one
+// 16-byte global load each, all NB x U of them issued before any is used; its 16 bf16 of a row
+// are two 16-byte LDS reads, made chunk by chunk as they are used (LDS is near: holding the x of
+// U chunks as well would only cost registers). The softmax `logits` get scale * S + bias.
+// NB is CS_NB for every row capacity, so chain_stage_workgroups' grid rule holds for both
+// forms; NB, U and the registers per row capacity: the file header.
+template <int M, int NB, int U>
+__device__ __forceinline__ void cs_layer_fp8(const ChainStage& p, const u16* xs, int rows,
+                                             char* dst, float* logits) {
+  const unsigned t = threadIdx.x;
+  const int lane = t & 63;
+  const unsigned char* q = (const unsigned char*)p.w;
+  for (int n0 = (blockIdx.x * CG_WAVES + (int)(t >> 6)) * NB; n0 < p.N;
+       n0 += gridDim.x * CG_WAVES * NB) {
+    float acc[NB][M];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[j][m] = 0.f;
+    for (int k0 = 0; k0 < p.K; k0 += C8_CHUNK * U) {
+      uint4 qv[NB][U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + u * C8_CHUNK + lane * 16;
+        if (k < p.K) {
+#pragma unroll
+          for (int j = 0; j < NB; ++j)  // (code 0 decodes to 0; a neuron past N is not written)
+            qv[j][u] = n0 + j < p.N ? *(const uint4*)(q + (long)(n0 + j) * p.ldw + k) : uint4{};
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + u * C8_CHUNK + lane * 16;
+        if (k < p.K) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {  // 8 columns at a time: x in registers for 8 only
+            bf16x8_t xv[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+              xv[m] = m < rows ? *(const bf16x8_t*)(xs + m * p.K + k + 8 * h) : bf16x8_t{};
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+              fp8_fma8<M>(h ? qv[j][u].z : qv[j][u].x, h ? qv[j][u].w : qv[j][u].y, xv, acc[j]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[j][m] = wave_sum(acc[j][m]);
+      const int n = n0 + j;
+      if (n < p.N && lane < rows) {
+        float v = 0.f;
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+          if (m == lane) v = acc[j][m];
+        v = __fmul_rn(p.w_scale[n], v);
+        v += p.bias ? p.bias[n] : 0.f;
+        if (logits) {
+          logits[lane * p.N + n] = v;
+        } else {
+          v = act_fwd(v, p.act);
+          if (p.out_f32)
+            ((float*)dst)[(long)lane * p.dst_ld + n] = v;
+          else
+            ((u16*)dst)[(long)lane * p.dst_ld + n] = f2bf(v);
+        }
+      }
+    }
+  }
+}
 
+constexpr int CS_NB = 4;  // neurons per wave in flight (chain_stage_kernel, both weight forms)
+
+// FP8: the layer reads e4m3 codes (cs_layer_fp8); everything else is shared.
+template <bool FP8>
 __global__ __launch_bounds__(256) void chain_stage_kernel(ChainStage p) {
   extern __shared__ __attribute__((aligned(16))) char cs_lds[];
   __shared__ uint32_t s_cmd[4];  // run, input status, rows, ack failure
@@ -438,12 +600,22 @@ __global__ __launch_bounds__(256) void chain_stage_kernel(ChainStage p) {
             __HIP_MEMORY_SCOPE_SYSTEM);
       }
       __syncthreads();
-      switch (rows) {
-        case 1: cs_layer<1, CS_NB>(p, xs, rows, dst, logits); break;
-        case 2: cs_layer<2, CS_NB>(p, xs, rows, dst, logits); break;
-        case 3:
-        case 4: cs_layer<4, CS_NB>(p, xs, rows, dst, logits); break;
-        default: cs_layer<8, CS_NB>(p, xs, rows, dst, logits); break;
+      if constexpr (FP8) {
+        switch (rows) {
+          case 1: cs_layer_fp8<1, CS_NB, 4>(p, xs, rows, dst, logits); break;
+          case 2: cs_layer_fp8<2, CS_NB, 4>(p, xs, rows, dst, logits); break;
+          case 3:
+          case 4: cs_layer_fp8<4, CS_NB, 2>(p, xs, rows, dst, logits); break;
+          default: cs_layer_fp8<8, CS_NB, 2>(p, xs, rows, dst, logits); break;
+        }
+      } else {
+        switch (rows) {
+          case 1: cs_layer<1, CS_NB>(p, xs, rows, dst, logits); break;
+          case 2: cs_layer<2, CS_NB>(p, xs, rows, dst, logits); break;
+          case 3:
+          case 4: cs_layer<4, CS_NB>(p, xs, rows, dst, logits); break;
+          default: cs_layer<8, CS_NB>(p, xs, rows, dst, logits); break;
+        }
       }
       if (logits) {  // row softmax (one workgroup): a wave per row
         __syncthreads();
@@ -587,16 +759,22 @@ int chain_gemv_send(const ChainGemvSend& p, hipStream_t stream) {
       p.ldw < p.K || p.ldx % 8 || p.ldw % 8 || p.dst_ld < p.N || misaligned16(p.x) ||
       misaligned16(p.w))
     return -2;
+  // fp8 rows: a lane's 16 codes are one aligned 16-byte load (ldw counts bytes)
+  if (p.w_scale && (p.K % 16 || p.ldw % 16)) return -2;
   // the folded receive makes every workgroup wait on the input flag: at most CG_RECV_WG of
   // them, so a node's worth of waiting stages (a one-GPU rehearsal puts 8 on one GPU) stays
   // far below what the GPU holds at once
   constexpr int CG_RECV_WG = 64;
   const int wg = (p.N + CG_WAVES - 1) / CG_WAVES;
   const dim3 grid(p.in_flag ? std::min(wg, CG_RECV_WG) : wg), block(256);
-#define DNN_CG(MM)                                                                           \
-  if (p.out_f32)                                                                             \
-    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, true>), grid, block, 0, stream, p);       \
-  else                                                                                       \
+#define DNN_CG(MM)                                                                            \
+  if (p.w_scale && p.out_f32)                                                                 \
+    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, true, true>), grid, block, 0, stream, p);  \
+  else if (p.w_scale)                                                                         \
+    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, false, true>), grid, block, 0, stream, p); \
+  else if (p.out_f32)                                                                         \
+    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, true>), grid, block, 0, stream, p);        \
+  else                                                                                        \
     hipLaunchKernelGGL((chain_gemv_send_kernel<MM, false>), grid, block, 0, stream, p);
   switch (p.rows) {
     case 1: DNN_CG(1) break;
@@ -625,6 +803,8 @@ int chain_stage_run(const ChainStage& p, int workgroups, int share, hipStream_t 
       p.dst_ld < p.N || p.nslot < 2 || p.max_rows < 1 || p.max_rows > GEMV_MAX_ROWS ||
       misaligned16(p.in_slots) || misaligned16(p.w) || p.epoch == 0)
     return -2;
+  if (p.w_scale && (p.K % 16 || p.ldw % 16)) return -2;  // fp8 rows, as chain_gemv_send
+  const auto kernel = p.w_scale ? chain_stage_kernel<true> : chain_stage_kernel<false>;
   const long lds = (long)p.max_rows * p.K * 2 +
                    (p.act == ACT_SOFTMAX ? (long)p.max_rows * p.N * 4 : 0);
   if (lds > 64 * 1024) return -3;  // rows staged in LDS: K (and a softmax's N) bounded
@@ -633,14 +813,14 @@ int chain_stage_run(const ChainStage& p, int workgroups, int share, hipStream_t 
   // completes only when all of a stage's workgroups count in, and resident ones never yield):
   // `share` stages split what the GPU holds, with a quarter kept for everything else
   int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chain_stage_kernel, 256,
-                                                   (size_t)lds) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, (size_t)lds) !=
+          hipSuccess ||
       hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return -9;
   const int cap = std::max(1, per_cu * cus * 3 / 4 / std::max(1, share));
   workgroups = std::min(workgroups, cap);
-  hipLaunchKernelGGL(chain_stage_kernel, dim3(workgroups), dim3(256), (size_t)lds, stream, p);
+  hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(256), (size_t)lds, stream, p);
   return hipGetLastError() == hipSuccess ? workgroups : -9;
 }
 

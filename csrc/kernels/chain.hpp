@@ -84,8 +84,8 @@ struct ChainGemvSend {
   const uint32_t* in_flag;   // nullptr: x is already local (chain_recv ran, or stage 0)
   const uint16_t* x;         // [rows][ldx] bf16 input rows
   long ldx;
-  const uint16_t* w;         // [N][ldw] bf16 weights (nn.Linear layout)
-  long ldw;
+  const uint16_t* w;         // [N][ldw] bf16 weights (nn.Linear layout); with w_scale: e4m3
+  long ldw;                  // codes, [N][ldw] BYTES (ldw % 16 == 0, K % 16 == 0)
   const float* bias;         // [N] or nullptr
   int act;                   // Act code (forward activation)
   int rows, N, K;            // rows <= GEMV_MAX_ROWS; K % 8 == 0
@@ -104,6 +104,9 @@ struct ChainGemvSend {
   uint32_t* prev_ack;
   uint32_t* counter;         // [2] zero-initialised, left zeroed: arrivals, ack failures
   unsigned long long timeout_ticks;
+  const float* w_scale;      // nullptr: bf16 weights. Else [N] fp32, one scale per output neuron
+                             // (ops.quant_rows_fp8's format), and the rows are gemv_fp8.hip's bit
+                             // for bit: act(fl32(w_scale[n] * S) + bias[n]), S in its lane order
 };
 int chain_gemv_send(const ChainGemvSend& p, hipStream_t stream);
 
@@ -123,7 +126,7 @@ struct ChainStage {
   const uint16_t* in_slots;  // [nslot][max_rows][ldx] bf16 rows (L2-uncached)
   long ldx;                  // elements (= K padded)
   uint32_t* prev_ack;        // producer's ack word (IPC-mapped)
-  const uint16_t* w;         // [N][ldw]
+  const uint16_t* w;         // [N][ldw] bf16; with w_scale: e4m3 codes, [N][ldw] BYTES
   long ldw;
   const float* bias;
   int act;                   // Act code; ACT_SOFTMAX: row softmax (one workgroup, N <= 1024)
@@ -144,6 +147,8 @@ struct ChainStage {
   uint32_t epoch;            // this launch's id (exit word value)
   int stage, nslot, max_rows;
   unsigned long long idle_ticks, timeout_ticks;
+  const float* w_scale;      // nullptr: bf16 weights. Else [N] fp32 row scales of the e4m3 codes
+                             // in w (K % 16 == 0, ldw % 16 == 0): gemv_fp8.hip's math, bitwise
 };
 // Returns the workgroups launched (>= 1; capped so that `share` persistent stages on this GPU
 // are all resident at once) or < 0 on a parameter / launch error.

@@ -107,6 +107,17 @@ class InferenceStage:
     def out_dim(self) -> int:
         return self.dims[-1]
 
+    def weight_operand(self, i: int):
+        """Layer i's weight operand for a kernel that reads the stage's weights in place (the
+        device-side chain): ``(tensor, row stride, (Np, Kp), scale)``. bf16: the padded weight,
+        its stride in elements, ``None``. fp8: the e4m3 codes, their stride in bytes, the fp32
+        row scales."""
+        if self.weights == "fp8":
+            q = self.q[i]
+            return q, q.stride(0), tuple(q.shape), self.s[i]
+        w = self.w[i]
+        return w, w.stride(0), tuple(w.shape), None
+
     def check_input_dim(self, cols: int) -> None:
         """Dimension walk of grpc_node.py:80-93 against the configured widths."""
         expected, cur = self.expected_input, cols

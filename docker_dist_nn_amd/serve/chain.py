@@ -40,6 +40,7 @@ the stage reports INTERNAL) or ``hang`` (the stage stops responding after
 from __future__ import annotations
 
 import argparse
+import collections
 from contextlib import nullcontext
 import itertools
 import json
@@ -99,6 +100,7 @@ class ChainRank:
         self.ret_group = dist.new_group(sorted({0, world - 1})) if world > 1 else None
         self.compute_lock = threading.Lock()
         self._ids = itertools.count(1)
+        self.lat: collections.deque = collections.deque(maxlen=100000)  # rank 0: seconds
         self._pending: dict[int, Future] = {}
         self._pending_lock = threading.Lock()
         self._sendq: "queue.Queue" = queue.Queue()
@@ -259,6 +261,7 @@ class ChainRank:
         self.stage.check_input_dim(cols)  # ValueError -> INVALID_ARGUMENT
         if self.fast is not None and rows <= self.small:
             return self.fast.predict(x, timeout)
+        t_in = time.perf_counter()
         if self.work_stream is not None:  # (an ingress worker thread: see work_stream)
             torch.cuda.set_stream(self.work_stream)
         R = bucket(rows)
@@ -295,7 +298,17 @@ class ChainRank:
             bad = self.names[hdr[4]] if 0 <= hdr[4] < len(self.names) else "stage"
             raise StageFailure(bad, _CODES.get(status, grpc.StatusCode.INTERNAL),
                                f"stage {bad} failed (status {status})")
-        return res[:rows].double().numpy()
+        res = res[:rows].double().numpy()
+        self.lat.append(time.perf_counter() - t_in)
+        return res
+
+    def latency_summary(self) -> str:
+        """Rank 0: percentiles of predict() on the message chain -- request in to logits out,
+        without the gRPC ingress around it (FastChain.latency_summary's counterpart)."""
+        t = np.asarray(self.lat, dtype=np.float64) * 1e3
+        p = np.percentile(t, [50, 90, 99])
+        return (f"message chain predict latency over {t.size} requests: p50 {p[0]:.4f} ms "
+                f"p90 {p[1]:.4f} ms p99 {p[2]:.4f} ms")
 
     def _sender(self) -> None:
         """Feeds the chain in request order (the only thread sending on the forward group)."""
@@ -334,6 +347,8 @@ class ChainRank:
     def stop_chain(self, timeout: float = 10.0) -> None:
         if self.fast is not None:
             self.fast.stop()
+        if self.rank == 0 and self.lat:
+            log.info(self.latency_summary())
         if self.world > 1:
             self._sendq.put(None)
             for t in self._threads:
@@ -456,10 +471,7 @@ def main(argv: Optional[list[str]] = None) -> int:
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))
     if world > 1 and use_gpu and switches.get("DNN_CHAIN_FAST") == "1":
-        if stage.weights == "fp8":  # the device-side chain reads bf16 weights (stage.w)
-            why = "fp8 weights (host chain)"
-        else:
-            why = cr.enable_fast()
+        why = cr.enable_fast()
         if rank == 0:
             log.info(f"({st['name']}) serving-size requests: {why}")
     log.info(f"({st['name']}) stage ready on {device}: {len(layers)} layer(s), "

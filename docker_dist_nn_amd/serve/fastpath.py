@@ -34,6 +34,11 @@ header read and a host send per hop. Here:
   softmax stage -- 1000 classes at 16 or more rows per request, say -- is refused there and
   served by the host-driven loop through ``InferenceStage.forward``, whose row softmax has no
   class limit (csrc/kernels/softmax_wide.hip beyond 256);
+* a stage serving from fp8 weights (``--weights fp8``) takes the same path: the fused send,
+  rank 0's native request and the persistent stage kernel read the e4m3 codes and their row
+  scales in place (``InferenceStage.weight_operand``, the kernels' ``w_scale``) and sum in
+  ``gemv_fp8``'s order, so a request's rows are bit for bit what ``ops.gemv_fp8`` -- the host
+  chain's layer -- gives;
 * larger requests and any set-up that cannot map its peers keep using the message-passing
   chain (serve/chain.py), which stays the fallback.
 """
@@ -444,7 +449,8 @@ class FastChain:
         L = len(st.layers)
         if L > 1:
             x = st.forward(rows, x=x, upto=L - 1)
-        w, b = st.w[-1], st.b[-1]
+        w, ldw, (n_pad, _), scale = st.weight_operand(L - 1)
+        b = st.b[-1]
         slot = seq % NSLOT
         dst, dld, dhdr, dflag = self._dst(slot)
         f32 = self.rank == self.world - 1  # the last rank fills rank 0's fp32 result slots
@@ -453,13 +459,14 @@ class FastChain:
             in_flag, prev_ack = _ptr(self.flags, F_IN + slot), self.prev_flags + 4 * F_ACK
         else:
             x_ptr, ldx, in_flag, prev_ack = x.data_ptr(), x.stride(0), 0, 0
-        self.n.chain_gemv_send(s.cuda_stream, x_ptr, ldx, w.data_ptr(), w.stride(0),
-                               b.data_ptr(), ops.kernels._act(st.acts[-1]), rows, w.shape[0],
+        self.n.chain_gemv_send(s.cuda_stream, x_ptr, ldx, w.data_ptr(), ldw,
+                               b.data_ptr(), ops.kernels._act(st.acts[-1]), rows, n_pad,
                                self.in_w if recv else x.shape[1], int(f32), dst,
                                dld // (4 if f32 else 2), dhdr, in_hdr, _ptr(self.flags, F_ERR),
                                self.rank, 0, self.ack_ptr,
                                (seq - NSLOT) & 0xFFFFFFFF, dflag, seq, prev_ack,
-                               self.counter.data_ptr(), self.cr.hop_timeout, in_flag=in_flag)
+                               self.counter.data_ptr(), self.cr.hop_timeout, in_flag=in_flag,
+                               w_scale=0 if scale is None else scale.data_ptr())
 
     # ---- rank 0 -------------------------------------------------------------------------------
     def predict(self, x: np.ndarray, timeout: Optional[float]) -> np.ndarray:
@@ -633,20 +640,22 @@ class FastChain:
         """Rank 0, one-layer stage, fused path: H2D + layer-and-send + result wait + D2H +
         ack + event as one native call (runtime/chain_host.cpp)."""
         st = self.cr.stage
-        w, b = st.w[0], st.b[0]
+        w, ldw, (n_pad, _), scale = st.weight_operand(0)
+        b = st.b[0]
         dst, dld, dhdr, dflag = self._dst(slot)
         base = self.res[slot]
         f32 = self.world == 1  # (rank 0 feeds rank 1's bf16 slot)
         self.host.request(
             slot, self.stream.cuda_stream, self.res_stream.cuda_stream, self.x0.data_ptr(),
-            self.h_in[slot].data_ptr(), rows * self.in_w * 2, w.data_ptr(), w.stride(0),
-            b.data_ptr(), ops.kernels._act(st.acts[0]), rows, w.shape[0], self.in_w, dst,
+            self.h_in[slot].data_ptr(), rows * self.in_w * 2, w.data_ptr(), ldw,
+            b.data_ptr(), ops.kernels._act(st.acts[0]), rows, n_pad, self.in_w, dst,
             dld // (4 if f32 else 2), dhdr, _ptr(self.flags, F_ERR), _ptr(self.flags, F_ACK),
             (seq - NSLOT) & 0xFFFFFFFF, dflag, seq, self.counter.data_ptr(),
             self.cr.hop_timeout, _ptr(self.flags, F_RES + slot), _ptr(base, 2),
             base.data_ptr(), self.h_out[slot].data_ptr(),
             HDR + rows * self.res_w * 4, self.prev_flags_of_last() + 4 * F_ACK,
-            self.cr.hop_timeout * self.world)
+            self.cr.hop_timeout * self.world,
+            w_scale=0 if scale is None else scale.data_ptr())
 
     def _result(self, seq: int, slot: int, rows: int, t_in: float) -> np.ndarray:
         """Decode the result slot's host copy (header, then fp32 rows) of request ``seq``."""
@@ -791,14 +800,16 @@ class FastChain:
             return False
         if self.cr.fault_stage == str(self.rank) or self.trace:
             return False  # fault injection and tracing act per request on the host
-        n = st.dims[-1] if st.acts[0] == "softmax" else st.w[0].shape[0]
+        n_pad, k_pad = st.weight_operand(0)[2]
+        n = st.dims[-1] if st.acts[0] == "softmax" else n_pad
         lds = self.max_rows * self.in_w * 2 + (self.max_rows * n * 4
                                                 if st.acts[0] == "softmax" else 0)
-        return lds <= 64 * 1024 and st.w[0].shape[1] == self.in_w
+        return lds <= 64 * 1024 and k_pad == self.in_w
 
     def _persist_launch(self, start: int, epoch: int) -> None:
         st = self.cr.stage
-        w, b, act = st.w[0], st.b[0], st.acts[0]
+        w, ldw, (n_pad, _), scale = st.weight_operand(0)
+        b, act = st.b[0], st.acts[0]
         last = self.rank == self.world - 1
         if last:  # rank 0's result slots: header, then fp32 rows
             dst, slot_b = self.dst + HDR, self.res_bytes
@@ -814,13 +825,14 @@ class FastChain:
         else:
             in_flags, in_hdrs = _ptr(self.flags, F_IN), _ptr(self.flags, F_HDR)
             in_slots, prev_ack = self.slots.data_ptr(), self.prev_flags + 4 * F_ACK
-        n_out = st.dims[-1] if act == "softmax" else w.shape[0]
+        n_out = st.dims[-1] if act == "softmax" else n_pad
         self.workgroups = self.n.chain_stage_run(
             self.pstream.cuda_stream, in_flags, in_hdrs, in_slots, self.in_w, prev_ack,
-            w.data_ptr(), w.stride(0), b.data_ptr(), ops.kernels._act(act), n_out, self.in_w,
+            w.data_ptr(), ldw, b.data_ptr(), ops.kernels._act(act), n_out, self.in_w,
             int(last), dst, slot_b, self.out_w, hdr, hstride, nflags, self.ack_ptr, self._ctl_dev,
             self._ctl_dev + 4, self.sync.data_ptr(), start & 0xFFFFFFFF, epoch, self.rank, NSLOT,
-            self.max_rows, PERSIST_IDLE_S, self.cr.hop_timeout, share=max(1, self.gpu_share))
+            self.max_rows, PERSIST_IDLE_S, self.cr.hop_timeout, share=max(1, self.gpu_share),
+            w_scale=0 if scale is None else scale.data_ptr())
 
     def _persist_loop(self) -> None:
         """Keep the stage kernel running until the ring stops: relaunch it after an idle exit,
