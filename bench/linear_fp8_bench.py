@@ -1,10 +1,13 @@
-"""fp8-weight forward layer at serving buckets of 64 .. 1024 rows: three ways to run one layer
+"""fp8-weight forward layer at serving buckets of 64 .. 65536 rows: the ways to run one layer
 on the same GPU in the same process, by the method of bench/gemv_fp8_bench.py.
 
-  bf16     ops.linear_fwd on bf16 weights (what --weights bf16 serves with);
-  scratch  ops.dequant_rows_fp8 of the whole layer into a bf16 buffer + ops.linear_fwd on it
-           (--weights fp8 --fp8-gemm scratch: the yardstick for FP8_DIRECT_MAX_ROWS);
-  direct   ops.linear_fwd_fp8 on the codes (csrc/kernels/linear_fp8.hip; --fp8-gemm direct).
+  bf16       ops.linear_fwd on bf16 weights (what --weights bf16 serves with);
+  scratch    ops.dequant_rows_fp8 of the whole layer into a bf16 buffer + ops.linear_fwd on it
+             (--weights fp8 --fp8-gemm scratch: the yardstick for FP8_DIRECT_MAX_ROWS);
+  direct     ops.linear_fwd_fp8 on the codes (csrc/kernels/linear_fp8.hip; --fp8-gemm direct);
+  w8a8       ops.linear_fwd_w8a8: ops.quant_rows_fp8 of the rows + ops.linear_w8a8 on codes x
+             codes (csrc/kernels/linear_w8a8.hip; --fp8-gemm w8a8) -- what a layer costs;
+  w8a8_gemm  ops.linear_w8a8 alone, on rows quantised beforehand.
 
 Two layers: 1024 x 1024 on ONE weight buffer (cache-resident: launch and latency) and 8192 x
 8192, where each contender rotates through enough distinct weight buffers (>= 3 x the 256-MiB
@@ -14,7 +17,10 @@ replayed (how the engine serves; no host work between kernels). Per case: the me
 rounds, each contender's run-to-run spread (max - min over the median), the ratios of the
 medians and the effective weight bytes/s (bytes of the resident weight format per call). One
 JSON line per case, printed and appended to ``--out``. ``--tiles 1,2`` adds direct contenders
-with a forced tile (linear_fp8.hpp) to compare against the launcher's choice."""
+with a forced tile (linear_fp8.hpp) and ``--w8a8-tiles 1,2`` w8a8_gemm contenders with a forced
+tile (linear_w8a8.hpp) to compare against the launchers' choices. Past 1024 rows the calls per
+timed loop shrink with the rows (a call then takes milliseconds) and the result check looks at
+the first 1024 rows."""
 from __future__ import annotations
 
 import argparse
@@ -79,7 +85,7 @@ def layer(N, K, cold, dev):
     return ws, qs, torch.empty(N, K, dtype=torch.bfloat16, device=dev)
 
 
-def run(N, K, cold, M, ws, qs, scratch, iters, rounds, tiles):
+def run(N, K, cold, M, ws, qs, scratch, iters, rounds, tiles, w8a8_tiles=()):
     dev = ws[0].device
     n_bf16, n_fp8 = len(ws), len(qs)
     g = torch.Generator(device=dev).manual_seed(N + M)
@@ -95,6 +101,19 @@ def run(N, K, cold, M, ws, qs, scratch, iters, rounds, tiles):
         return lambda k: ops.linear_fwd_fp8(x, qs[k % n_fp8][0], qs[k % n_fp8][1], bias, y,
                                             "relu", tile=tile)
 
+    xq = torch.empty(M, K, dtype=torch.uint8, device=dev)
+    sx = torch.empty(M, dtype=torch.float32, device=dev)
+    xq0, sx0 = torch.empty_like(xq), torch.empty_like(sx)  # quantised once, for w8a8_gemm
+    ops.quant_rows_fp8(x, xq0, sx0)
+
+    def make_w8a8(y):
+        return lambda k: ops.linear_fwd_w8a8(x, qs[k % n_fp8][0], qs[k % n_fp8][1], bias, y,
+                                             "relu", xq=xq, sx=sx)
+
+    def make_w8a8_gemm(tile, y):
+        return lambda k: ops.linear_w8a8(xq0, sx0, qs[k % n_fp8][0], qs[k % n_fp8][1], bias, y,
+                                         "relu", tile=tile)
+
     yb, ysc = out("bf16"), out("scratch")
 
     def bf16(k):
@@ -108,19 +127,33 @@ def run(N, K, cold, M, ws, qs, scratch, iters, rounds, tiles):
            "direct": (make_direct(0, out("direct")), n_fp8)}
     for t in tiles:
         fns[f"direct_t{t}"] = (make_direct(t, out(f"direct_t{t}")), n_fp8)
+    fns["w8a8"] = (make_w8a8(out("w8a8")), n_fp8)
+    fns["w8a8_gemm"] = (make_w8a8_gemm(0, out("w8a8_gemm")), n_fp8)
+    for t in w8a8_tiles:
+        fns[f"w8a8_gemm_t{t}"] = (make_w8a8_gemm(t, out(f"w8a8_gemm_t{t}")), n_fp8)
 
-    # same results first: direct against fp64 over the decoded codes (first 256 neurons), and
-    # every fp8 contender against the bf16 layer within the format's 2^-4 per weight
+    # same results first (rows up to 1024): direct against fp64 over the decoded codes (first
+    # 256 neurons), w8a8 against fp64 over the decoded codes of both operands, and every fp8
+    # contender against the bf16 layer within the format's 2^-4 per weight (w8a8: per weight
+    # and per activation)
     for fn, _ in fns.values():
         fn(0)
     q, s = qs[0]
-    dec = ref.e4m3_table().to(dev)[q[:256].long()] * s[:256, None].double()
-    want = torch.relu(x.double() @ dec.t() + bias[:256].double())
-    mag = x.float().abs() @ ws[0].float().abs().t()
+    R = min(M, 1024)
+    table = ref.e4m3_table().to(dev)
+    dec = table[q[:256].long()] * s[:256, None].double()
+    want = torch.relu(x[:R].double() @ dec.t() + bias[:256].double())
+    want8 = torch.relu((table[xq0[:R].long()] * sx0[:R, None].double()) @ dec.t()
+                       + bias[:256].double())
+    mag = x[:R].float().abs() @ ws[0].float().abs().t()
     for name, y in ys.items():
         if name.startswith("direct"):
-            torch.testing.assert_close(y[:, :256].double(), want, rtol=2.0 ** -7, atol=1e-3)
-        assert bool(((y.float() - yb.float()).abs() <= 2.0 ** -3 * mag + 1e-2).all()), name
+            torch.testing.assert_close(y[:R, :256].double(), want, rtol=2.0 ** -7, atol=1e-3)
+        if name.startswith("w8a8"):
+            torch.testing.assert_close(y[:R, :256].double(), want8, rtol=2.0 ** -7, atol=1e-3)
+        tol = 2.0 ** -2 if name.startswith("w8a8") else 2.0 ** -3
+        assert bool(((y[:R].float() - yb[:R].float()).abs() <= tol * mag + 1e-2).all()), name
+    del want, want8, mag, dec
 
     stream = torch.cuda.Stream(dev)
     torch.cuda.synchronize()
@@ -146,6 +179,15 @@ def run(N, K, cold, M, ws, qs, scratch, iters, rounds, tiles):
         res[f"{name}_spread"] = round(_spread(ts[name]), 3)
         res[f"{name}_weight_TBps"] = round(N * K * (2 if name == "bf16" else 1) / med[name] / 1e6,
                                            3)
+    def beats(a, b):  # a beats b by more than the larger of the two spreads
+        return bool(med[b] - med[a] >
+                    max(_spread(ts[a]) * med[a], _spread(ts[b]) * med[b]))
+
+    for other in ("bf16", "scratch", "direct"):
+        res[f"w8a8_over_{other}"] = round(med["w8a8"] / med[other], 3)
+        res[f"w8a8_beats_{other}"] = beats("w8a8", other)
+        res[f"{other}_beats_w8a8"] = beats(other, "w8a8")
+    res["w8a8_gemm_over_bf16"] = round(med["w8a8_gemm"] / med["bf16"], 3)
     res["direct_over_scratch"] = round(med["direct"] / med["scratch"], 3)
     res["direct_over_bf16"] = round(med["direct"] / med["bf16"], 3)
     res["scratch_over_bf16"] = round(med["scratch"] / med["bf16"], 3)
@@ -161,22 +203,26 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=0,
                     help="calls per timed loop (default: 1000 cache-resident, 120 cold)")
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--rows", type=str, default="64,128,256,512,1024",
+    ap.add_argument("--rows", type=str, default="64,128,256,512,1024,2048,4096,16384,65536",
                     help="input row counts, comma-separated")
     ap.add_argument("--tiles", type=str, default="", help="forced direct tiles to add, e.g. 1,2")
+    ap.add_argument("--w8a8-tiles", type=str, default="",
+                    help="forced w8a8_gemm tiles to add, e.g. 1,2")
     ap.add_argument("--out", type=str, default=OUT_DEFAULT)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("linear_fp8_bench needs a GPU: nothing is measured without one")
     tiles = [int(t) for t in a.tiles.split(",") if t]
+    w8a8_tiles = [int(t) for t in a.w8a8_tiles.split(",") if t]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     dev = torch.device("cuda")
     with open(a.out, "a") as f:
         for N, K, cold in CASES:
             ws, qs, scratch = layer(N, K, cold, dev)
             for M in map(int, a.rows.split(",")):
-                iters = a.iters or (120 if cold else 1000)
-                line = json.dumps(run(N, K, cold, M, ws, qs, scratch, iters, a.rounds, tiles))
+                iters = a.iters or max(8, (120 if cold else 1000) * 1024 // max(M, 1024))
+                line = json.dumps(run(N, K, cold, M, ws, qs, scratch, iters, a.rounds, tiles,
+                                      w8a8_tiles))
                 print(line, flush=True)
                 f.write(line + "\n")
                 f.flush()

@@ -49,10 +49,12 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="serving weight format: fp8 = e4m3 codes + one scale per output neuron "
                          "(half the resident bytes; requests of <= 8 rows stream them directly)")
-    ap.add_argument("--fp8-gemm", choices=["scratch", "direct"], default="scratch",
+    ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --weights fp8, buckets of more than 8 rows: scratch = dequantise "
                          "the layer into a bf16 buffer + the bf16 GEMM; direct = the fp8-weight "
-                         "GEMM on the codes, up to ops.FP8_DIRECT_MAX_ROWS rows")
+                         "GEMM on the codes, up to ops.FP8_DIRECT_MAX_ROWS rows; w8a8 = also "
+                         "quantises the activations of every layer to e4m3 (one scale per row) "
+                         "and multiplies codes by codes on the fp8 MFMA, at any number of rows")
     ap.add_argument("--port", type=int, default=5101)
     ap.add_argument("--layer-distribution", type=str, default=None,
                     help="override, e.g. '[1,1,1]'")

@@ -43,9 +43,9 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--device", default="auto")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="with --local: the engine's weight format")
-    ap.add_argument("--fp8-gemm", choices=["scratch", "direct"], default="scratch",
+    ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --local --weights fp8: how buckets of more than 8 rows run "
-                         "(InferenceStage)")
+                         "(InferenceStage); w8a8 also quantises the activations to e4m3")
     ap.add_argument("--metrics-json", type=str, default=None)
     return ap
 

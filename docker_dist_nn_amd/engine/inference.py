@@ -33,7 +33,7 @@ from .. import switches
 
 
 WEIGHT_FORMATS = ("bf16", "fp8")
-FP8_GEMMS = ("scratch", "direct")
+FP8_GEMMS = ("scratch", "direct", "w8a8")
 
 
 class InferenceStage:
@@ -59,6 +59,22 @@ class InferenceStage:
     bf16 copy of a layer is written (such a bucket never allocates the scratch). Larger buckets
     keep the scratch path: at thousands of rows the GEMM is compute-bound and the detour is
     amortised. ``"scratch"`` (the default) is the path above for every bucket over 8 rows.
+
+    ``fp8_gemm="w8a8"`` (with ``weights="fp8"``; ignored with bf16) serves every bucket of more
+    than ``ops.GEMV_MAX_ROWS`` rows, with no row cap, from fp8 ACTIVATIONS as well: each layer
+    is ``ops.quant_rows_fp8`` of its input buffer (e4m3 codes plus one fp32 scale per row, the
+    pipeline-hop format) followed by ``ops.linear_w8a8``, which multiplies codes by codes on the
+    fp8 MFMA and applies both scales once per output. The code and scale buffers of every layer
+    live in ``buffers(rows)``: allocated with the bucket and reused in stream order, so graph
+    capture and native replay stay valid, and such a stage never allocates the bf16 scratch. The
+    quantiser runs over the input's padded width exactly as the buffer stands: pad columns hold
+    act(0) of the previous layer -- 0.5 after a sigmoid layer -- and meet zero weight codes, so
+    they add nothing to any sum and can only enter the row's amax (a row whose real entries are
+    all below 0.5 is then quantised on a coarser grid than it needs). Requests of <= 8 rows keep
+    ``ops.gemv_fp8`` on bf16 activations (they are bound by weight bytes; the device-side chain
+    is untouched), so answers on the two sides of the 8/9-row line differ within the activation
+    format's bound (2^-4 relative per element plus half a subnormal step of the row); for
+    ``"direct"`` they do not.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
@@ -135,7 +151,11 @@ class InferenceStage:
         if b is None:
             dev = self.device
             b = {"x": torch.zeros(rows, self.pads[0], dtype=torch.bfloat16, device=dev),
-                 "h": [], "f32": []}
+                 "h": [], "f32": [], "xq": [], "sx": []}
+            if self._w8a8(rows):  # every layer's input as e4m3 codes + one fp32 scale per row
+                for kp in self.pads[:-1]:
+                    b["xq"].append(torch.zeros(rows, kp, dtype=torch.uint8, device=dev))
+                    b["sx"].append(torch.zeros(rows, dtype=torch.float32, device=dev))
             for i, np_ in enumerate(self.pads[1:]):
                 last = i == len(self.layers) - 1
                 need_f32 = (last and self.is_last) or self.acts[i] == "softmax"
@@ -145,12 +165,21 @@ class InferenceStage:
             self._bufs[rows] = b
         return b
 
+    def _w8a8(self, rows: int) -> bool:
+        """Whether a bucket of ``rows`` rows runs on fp8 activations."""
+        return (self.weights == "fp8" and self.fp8_gemm == "w8a8"
+                and rows > ops.GEMV_MAX_ROWS)
+
     def _linear(self, i: int, x: torch.Tensor, y: torch.Tensor, act: str) -> None:
         """y = act(x . W_i^T + b_i) from the stage's weight format."""
         if self.weights == "bf16":
             ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
         elif x.shape[0] <= ops.GEMV_MAX_ROWS:
             ops.gemv_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
+        elif self.fp8_gemm == "w8a8":
+            b = self.buffers(x.shape[0])
+            ops.linear_fwd_w8a8(x, self.q[i], self.s[i], self.b[i], y, act=act, xq=b["xq"][i],
+                                sx=b["sx"][i])
         elif self.fp8_gemm == "direct" and x.shape[0] <= ops.FP8_DIRECT_MAX_ROWS:
             ops.linear_fwd_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
         else:
@@ -198,7 +227,7 @@ class InferenceEngine:
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch"):
-        """``weights``: "bf16" or "fp8", ``fp8_gemm``: "scratch" or "direct" (see
+        """``weights``: "bf16" or "fp8", ``fp8_gemm``: "scratch", "direct" or "w8a8" (see
         :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []

@@ -5,7 +5,7 @@ from .kernels import (FP8_DIRECT_MAX_ROWS, FP8_MAX, FP8_TINY_AMAX, KMAJ, MNMAJ, 
                       relu_mask_bits, FragMask,
                       colsum_partial, dact_colsum, dense_loss, dense_loss_col_chunks,
                       dense_loss_row_blocks, check_dense_loss, dequant_rows_fp8, quant_rows_fp8,
-                      gemm, gemv, gemv_fp8, linear_dgrad, linear_fwd, linear_fwd_fp8, linear_fwd_xent,
+                      gemm, gemv, gemv_fp8, linear_dgrad, linear_fwd, linear_fwd_fp8, linear_fwd_w8a8, linear_fwd_xent, linear_w8a8,
                       linear_wgrad, linear_wgrad_group, linear_wgrad_streamk, mlp_tail, pack_bf16,
                       reduce_multi, reduce_slabs, sgd_update, softmax_rows, softmax_xent,
                       step_advance, streamk_partial_elems, streamk_tiles, tail_blocks,
@@ -16,7 +16,7 @@ __all__ = ["FP8_DIRECT_MAX_ROWS", "FP8_MAX", "FP8_TINY_AMAX", "GEMV_MAX_ROWS", "
            "relu_mask_bits", "FragMask", "frag_mask_tiles", "GemmPlan", "gemm_plan", "plan",
            "colsum_partial", "dact_colsum", "dense_loss", "dense_loss_col_chunks",
            "dense_loss_row_blocks", "check_dense_loss", "dequant_rows_fp8", "quant_rows_fp8",
-           "dgrad_tiles", "gemm", "gemv", "gemv_fp8", "linear_dgrad", "linear_fwd", "linear_fwd_fp8", "linear_fwd_xent",
+           "dgrad_tiles", "gemm", "gemv", "gemv_fp8", "linear_dgrad", "linear_fwd", "linear_fwd_fp8", "linear_fwd_w8a8", "linear_fwd_xent", "linear_w8a8",
            "linear_wgrad", "linear_wgrad_group", "linear_wgrad_streamk", "mlp_tail", "pack_bf16", "pick_splits", "pick_tiles",
            "reduce_multi", "reduce_slabs", "sgd_update", "softmax_rows", "softmax_xent",
            "step_advance", "streamk_partial_elems", "streamk_tiles", "tail_blocks", "tail_supported",

@@ -510,6 +510,56 @@ def linear_fwd_fp8(x, q, scale, bias, y, act="relu", tile=0):
     return y
 
 
+def linear_w8a8(xq, sx, q, scale, bias, y, act="relu", tile=0):
+    """Forward layer with e4m3 codes on both operands, each in the format of quant_rows_fp8:
+    y[m][n] = act(fl32(sx[m] * fl32(scale[n] * sum_k e4m3(xq[m][k]) * e4m3(q[n][k]))) + bias[n])
+    on the fp8 MFMA (csrc/kernels/linear_w8a8.hip): the weight scale first, the row scale
+    second, each a rounded fp32 multiply of its own. xq uint8 [M][>=K] codes of the rows, sx fp32
+    [>=M], q uint8 [N][>=K] codes of the weights, scale fp32 [>=N], y bf16 or fp32; K % 16 == 0,
+    rows of codes 16-byte aligned, any M >= 1.
+    ``tile``: 0 = chosen by the launcher, 1 / 2 force one (linear_w8a8.hpp; tests, benchmark)."""
+    M, K = xq.shape
+    N = q.shape[0]
+    if K % 16:
+        raise ValueError("linear_w8a8 takes K % 16 == 0")
+    _rows(xq, "xq", torch.uint8)
+    _rows(q, "q", torch.uint8)
+    if q.shape[1] < K or y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("linear_w8a8 operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if sx.dtype != torch.float32 or sx.numel() < M or not sx.is_contiguous():
+        raise ValueError("sx must be contiguous fp32 with >= M entries")
+    if scale.dtype != torch.float32 or scale.numel() < N or not scale.is_contiguous():
+        raise ValueError("scale must be contiguous fp32 with >= N entries")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not xq.is_cuda:
+        return ref.linear_w8a8(xq, sx, q, scale, bias, y, M, N, K, _act(act))
+    native().linear_w8a8(_p(xq), xq.stride(0), _p(sx), _p(q), q.stride(0), _p(scale), _p(bias),
+                         _p(y), y.stride(0), M, N, K, _act(act), int(y.dtype == torch.float32),
+                         _stream(xq), tile)
+    return y
+
+
+def linear_fwd_w8a8(x, q, scale, bias, y, act="relu", xq=None, sx=None, tile=0):
+    """A layer served with fp8 activations: quant_rows_fp8(x) into ``xq`` / ``sx`` (uint8
+    [>=M][>=K] with 16-byte aligned rows and fp32 [>=M]; temporaries when not given), then
+    linear_w8a8 on them. x bf16 [M][K]; everything else as linear_w8a8. Every column of x enters
+    its row's amax, so the answer differs from linear_fwd_fp8's within the activation format's
+    bound (tests/_fp8_oracle.round_trip_bound) unless the quantiser loses nothing."""
+    M, K = x.shape
+    if K % 16:
+        raise ValueError("linear_fwd_w8a8 takes K % 16 == 0")
+    _rows(x, "x", torch.bfloat16)
+    if xq is None:
+        xq = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    if sx is None:
+        sx = torch.empty(M, dtype=torch.float32, device=x.device)
+    quant_rows_fp8(x, xq, sx)
+    return linear_w8a8(xq[:M, :K], sx, q, scale, bias, y, act, tile)
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

@@ -97,6 +97,19 @@ def gemv_fp8(x, q, scale, bias, y, M, N, K, act):
     return y
 
 
+def linear_w8a8(xq, sx, q, sw, bias, y, M, N, K, act):
+    """y[:M, :N] = act(fl32(sx * fl32(sw * fl32(S))) + bias), S = dec(xq) . dec(q)^T in fp64: the
+    sum of the kernel (csrc/kernels/linear_w8a8.hip) without its summation error, then the
+    kernel's fp32 epilogue -- the weight scale first, the row scale second, each multiply
+    rounded on its own."""
+    S = _E4M3[xq[:M, :K].long()] @ _E4M3[q[:N, :K].long()].t()
+    v = sx[:M].float()[:, None] * (sw[:N].float() * S.float())
+    if bias is not None:
+        v = v + bias[:N].float()
+    y[:M, :N] = act_fwd(v, act).to(y.dtype)
+    return y
+
+
 def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
                  rows_per_block=64, colsum=None):
     rows, width = dz.shape
