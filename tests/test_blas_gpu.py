@@ -89,6 +89,7 @@ def test_engine_blas_steps_match_mfma_steps(dev, monkeypatch, model):
             tr.set_batch(xb, yb)
             tr.step()
             losses.append(tr.loss())
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     for a, b in zip(res[0][0], res[1][0]):
         assert abs(a - b) <= 2e-3 * abs(a) + 1e-4

@@ -227,6 +227,7 @@ def test_engine_tail_matches_unfused_training(dev, monkeypatch, num_micro):
             tr.set_batch(xb, yb)
             tr.step()
             losses.append(tr.loss())
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     for a, b in zip(res[0][0], res[1][0]):
         assert abs(a - b) <= 1e-4 * abs(a) + 1e-5

@@ -37,6 +37,7 @@ def test_overlap_plan_bitwise(dev, monkeypatch, model, rows):
             losses.append(tr.loss())
         plan = tr.executor._native_plan()
         assert any(seg == "@fork" for _, seg, _ in plan) == (flag != "0")
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     for r in res[1:]:
         assert res[0][0] == r[0]
@@ -72,6 +73,7 @@ def test_mode5_without_tail_bitwise(dev, monkeypatch):
         if flag == "5":
             assert segs.index("B0.L3") < segs.index("W2") and \
                 "@fork" in segs[segs.index("B0.L3"):segs.index("W2")], segs
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     assert res[0][0] == res[1][0]
     assert torch.equal(res[0][1], res[1][1])
@@ -136,6 +138,7 @@ def test_cross_step_overlap_bitwise(dev, monkeypatch):
             segs = [seg for _, seg, _ in tr.executor._xstep_plan(tr.executor._native_plan())]
             assert ("@xwait:w" in segs) == (dbl == "0") and segs[-1] == "@xmark:end", segs
             assert tr.stages[0].h0_double == (dbl == "1")
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     for r in res[1:]:  # DNN_XSTEP and DNN_H0_DOUBLE: bitwise the same training
         assert r[0] == res[0][0]

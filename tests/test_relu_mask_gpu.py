@@ -76,6 +76,7 @@ def test_engine_mask_path_bitwise_equals_activation_path(dev, monkeypatch):
             tr.set_batch(xb, yb)
             tr.step()
             losses.append(tr.loss())
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     assert res[0][0] == res[1][0]
     assert torch.equal(res[0][1], res[1][1])
@@ -110,6 +111,7 @@ def test_engine_fragment_mask_bitwise_equals_activation_path(dev, monkeypatch):
             tr.set_batch(xb, yb)
             tr.step()
             losses.append(tr.loss())
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
         del tr
     assert res[0][0] == res[1][0]

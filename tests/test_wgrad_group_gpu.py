@@ -57,6 +57,7 @@ def test_engine_grouped_wgrad_bitwise(dev, monkeypatch, model, batch, opt):
             tr.set_batch(xb, yb)
             tr.step()
             losses.append(tr.loss())
+        tr.flush()  # the step's side-stream update is ordered before the read
         res.append((losses, tr.stages[0].params.master.clone()))
     assert res[0][0] == res[1][0]
     assert torch.equal(res[0][1], res[1][1])
