@@ -14,6 +14,15 @@ from ..models.mlp import LayerGeom, round_up
 from .optimizer import OptimConfig, Optimizer
 
 _ALIGN = 64  # elements; keeps every layer's region 256-B aligned
+# Bias of the padding units of a sigmoid layer (width not a multiple of 64). With a zero bias they
+# would output sigmoid(0) = 0.5, the next layer's padded weight columns would receive the gradient
+# 0.5 * sum(dZ) and stop being zero: the padded model would drift away from the specified one (and
+# from what export() returns). At this bias their output is exactly 0 and so is their derivative
+# y (1 - y): every gradient of the padding stays exactly 0. Weight decay (and an L2 term under
+# Adam) would move the entries like any other bias, so every update is followed by
+# StageParams.pin_padding, which writes them back: the off-state does not depend on the step
+# count. A power of two: exact in bf16 (the pin's source) and fp32; its square is finite.
+PAD_OFF_BIAS = -2.0 ** 50
 
 
 def _of_opt(name: str) -> property:
@@ -64,6 +73,17 @@ class StageParams:
         # transposed bf16 weight shadows W^T[Kp][Np] of the layers whose dgrad reads them
         # (enable_wt); refreshed after every update of their layer (refresh_t)
         self.wt: dict[int, torch.Tensor] = {}
+        # padding-unit biases held at PAD_OFF_BIAS: layer -> (fp32 master entries, bf16 shadow
+        # entries, bf16 source of the pin), each [1][np_ - out_dim]
+        self.pad_pins: dict[int, tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
+        for i, g in enumerate(self.geoms):
+            n = g.np_ - g.spec.out_dim
+            if g.spec.activation == "sigmoid" and n:
+                lo = self.b_off[i] + g.spec.out_dim
+                self.pad_pins[i] = (self.master[lo:lo + n].view(1, n),
+                                    self.shadow[lo:lo + n].view(1, n),
+                                    torch.full((1, n), PAD_OFF_BIAS, dtype=torch.bfloat16,
+                                               device=device))
         # layers whose weight gradient GEMM applies the SGD step itself (Stage.enable_fused_
         # wgrad_update): the per-step update paths below skip their weights and W^T
         self.fused_layers: set[int] = set()
@@ -131,7 +151,7 @@ class StageParams:
     def load(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray]) -> None:
         """Set from unpadded [out][in] weights / [out] biases (any float dtype)."""
         self._load_flat(self.master, weights, biases, "weight")
-        self.refresh_shadow()
+        self.refresh_shadow()  # (pins the padding biases too)
 
     def init_default(self, seed: int) -> None:
         """nn.Linear default init, U(-1/sqrt(in), 1/sqrt(in)); seeded by GLOBAL layer index so
@@ -156,12 +176,26 @@ class StageParams:
 
     def refresh_t(self, a: int = 0, b: Optional[int] = None, step: bool = False,
                   skip: frozenset = frozenset()) -> None:
-        """Re-derive W^T of the local layers [a, b) that keep one (after their update).
+        """Re-derive W^T of the local layers [a, b) that keep one (after their update), and
+        re-pin their padding biases (pin_padding).
         ``step``: a per-step update -- layers updated by their wgrad epilogue (which writes
         W^T itself) are skipped; so are the ``skip`` layers (W^T written by the update)."""
         b = len(self.geoms) if b is None else b
         ops.transpose_multi([(self.wbf(i), self.wt[i]) for i in range(a, b) if i in self.wt and
                              i not in skip and not (step and i in self.fused_layers)])
+        self.pin_padding(a, b)
+
+    def pin_padding(self, a: int = 0, b: Optional[int] = None) -> None:
+        """Write the padding-unit biases of the sigmoid layers in [a, b) back to PAD_OFF_BIAS
+        (master and shadow): two copy launches per such layer, none for any other model. Runs
+        after every update of those layers (through refresh_t), so it is recorded / captured
+        with the update it follows."""
+        b = len(self.geoms) if b is None else b
+        for i in range(a, b):
+            if i in self.pad_pins:
+                m, sh, src = self.pad_pins[i]
+                ops.unpack_bf16(src, m)
+                ops.pack_bf16(m, sh)
 
     def _layers_of(self, e0: int, e1: int) -> tuple[int, int]:
         """Local layers whose parameters lie in the flat element range [e0, e1)."""

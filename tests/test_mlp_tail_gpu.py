@@ -9,6 +9,7 @@ import torch
 
 import _act_oracle as ao
 import _loss_oracle as lo
+from _step_audit import assert_dgrad_fp64 as _assert_dgrad_fp64
 from docker_dist_nn_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -126,25 +127,6 @@ def _exact_case(rows, k3, n3, n4, n_cls, act2, seed):
     labels = torch.randint(0, n_cls, (rows,), generator=g, dtype=torch.int32)
     labels[::7] = -1
     return x.to(torch.bfloat16), w3.to(torch.bfloat16), b3, w4.to(torch.bfloat16), b4, labels
-
-
-def _assert_dgrad_fp64(name, got, dz, w, y, act):
-    """A dgrad output against fp64 evaluated from the kernel's OWN stored inputs: 2 bf16 ulps
-    (the single rounding of the result, and slack for a rounding boundary) plus an absolute
-    floor for the fp32 accumulation, whose error scales with the sum of |terms|, not with the
-    result: 4 x the largest |fp32 - fp64| of the CPU reference path (ops/reference.py) on the
-    same inputs. Returns the floor."""
-    from docker_dist_nn_amd.models.mlp import ACT_CODE
-    from docker_dist_nn_amd.ops import reference as ref
-
-    dz, w, y, got = (t.detach().cpu() for t in (dz, w, y, got))
-    want = ao.act_bwd(dz.double() @ w.double(), y, act)
-    f32 = ref.act_bwd(dz.float() @ w.float(), y.float(), ACT_CODE[act])
-    floor = 4.0 * float((f32.double() - want).abs().max())
-    excess = (got.double() - want).abs() - (2.0 * ao.bf16_ulp(want) + floor)
-    assert not torch.isnan(got.float()).any()
-    assert float(excess.max()) <= 0.0, (name, act, float(excess.max()), floor)
-    return floor
 
 
 GEOS = [(128, 64, 64, 10), (256, 64, 64, 10), (64, 128, 64, 10), (128, 128, 128, 16),
