@@ -22,9 +22,11 @@
 #include "kernels/gemm.hpp"
 #include "kernels/gemv.hpp"
 #include "kernels/gemv_fp8.hpp"
+#include "kernels/gemv_mxfp4.hpp"
 #include "kernels/linear_fp8.hpp"
 #include "kernels/linear_w8a8.hpp"
 #include "kernels/mlp_tail.hpp"
+#include "kernels/mxfp4.hpp"
 #include "runtime/blaslt.hpp"
 #include "runtime/chain_host.hpp"
 #include "runtime/graph.hpp"
@@ -197,6 +199,24 @@ PYBIND11_MODULE(_native, m) {
             stream);
       },
       py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("ldq"), py::arg("scale"),
+      py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
+      py::arg("act"), py::arg("out_f32"), py::arg("stream"));
+  m.def(
+      "gemv_mxfp4",
+      [](uintptr_t x, long ldx, uintptr_t q, long ldq, uintptr_t e, long lde, uintptr_t bias,
+         uintptr_t y, long ldy, int M, int N, int K, int act, int out_f32, uintptr_t stream) {
+        launch(
+            "gemv_mxfp4",
+            [=](hipStream_t s, const dnn::Program& R) {
+              return dnn::gemv_mxfp4(R.fix(P<const uint16_t>(x)), ldx,
+                                     R.fix(P<const unsigned char>(q)), ldq,
+                                     R.fix(P<const unsigned char>(e)), lde,
+                                     R.fix(P<const float>(bias)), R.fix(P<void>(y)), ldy, M, N, K,
+                                     act, out_f32, s);
+            },
+            stream);
+      },
+      py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("ldq"), py::arg("e"), py::arg("lde"),
       py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("act"), py::arg("out_f32"), py::arg("stream"));
   m.def(
@@ -676,6 +696,28 @@ PYBIND11_MODULE(_native, m) {
           return dnn::dequant_rows_fp8(R.fix(P<const unsigned char>(q)), ldq,
                                        R.fix(P<const float>(scale)), rows, cols,
                                        R.fix(P<uint16_t>(x)), ldx, s);
+        },
+        stream);
+  });
+  m.def("quant_rows_mxfp4", [](uintptr_t x, long ldx, int rows, int cols, uintptr_t q, long ldq,
+                               uintptr_t e, long lde, uintptr_t stream) {
+    launch(
+        "quant_rows_mxfp4",
+        [=](hipStream_t s, const dnn::Program& R) {
+          return dnn::quant_rows_mxfp4(R.fix(P<const uint16_t>(x)), ldx, rows, cols,
+                                       R.fix(P<unsigned char>(q)), ldq,
+                                       R.fix(P<unsigned char>(e)), lde, s);
+        },
+        stream);
+  });
+  m.def("dequant_rows_mxfp4", [](uintptr_t q, long ldq, uintptr_t e, long lde, int rows,
+                                 int cols, uintptr_t x, long ldx, uintptr_t stream) {
+    launch(
+        "dequant_rows_mxfp4",
+        [=](hipStream_t s, const dnn::Program& R) {
+          return dnn::dequant_rows_mxfp4(R.fix(P<const unsigned char>(q)), ldq,
+                                         R.fix(P<const unsigned char>(e)), lde, rows, cols,
+                                         R.fix(P<uint16_t>(x)), ldx, s);
         },
         stream);
   });

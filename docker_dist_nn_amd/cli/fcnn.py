@@ -46,9 +46,13 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "workers: one gRPC stage process per stage on the reference's env "
                          "contract (grpc_node.py), chained over gRPC")
     ap.add_argument("--device", default="auto", help="auto | cpu | cuda")
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                     help="serving weight format: fp8 = e4m3 codes + one scale per output neuron "
-                         "(half the resident bytes; requests of <= 8 rows stream them directly)")
+                         "(half the resident bytes; requests of <= 8 rows stream them directly); "
+                         "mxfp4 = OCP microscaling FP4, 4-bit e2m1 codes + one e8m0 scale per 32 "
+                         "columns (17/64 of the resident bytes, streamed directly at <= 8 rows; "
+                         "coarse: up to a quarter of a weight or of its block's scale per "
+                         "weight, no calibration)")
     ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --weights fp8, buckets of more than 8 rows: scratch = dequantise "
                          "the layer into a bf16 buffer + the bf16 GEMM; direct = the fp8-weight "

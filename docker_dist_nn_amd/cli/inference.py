@@ -41,8 +41,9 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--local", type=str, default=None,
                     help="model config JSON: run the MI355X engine in-process, no server")
     ap.add_argument("--device", default="auto")
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
-                    help="with --local: the engine's weight format")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="with --local: the engine's weight format (fp8 = e4m3 codes + row "
+                         "scales; mxfp4 = 4-bit e2m1 codes + one e8m0 scale per 32 columns)")
     ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --local --weights fp8: how buckets of more than 8 rows run "
                          "(InferenceStage); w8a8 also quantises the activations to e4m3")

@@ -14,7 +14,9 @@ stage is a slice of layers on one GPU:
   captured once in a HIP graph, so a batch-1 request is a single graph launch.
 
 ``weights="fp8"`` holds the weights as OCP e4m3 codes plus one fp32 scale per output neuron
-(the format of ``ops.quant_rows_fp8``) instead of bf16: see :class:`InferenceStage`.
+(the format of ``ops.quant_rows_fp8``) instead of bf16, ``weights="mxfp4"`` as OCP MXFP4 (4-bit
+e2m1 codes plus one e8m0 scale byte per 32 columns, the format of ``ops.quant_rows_mxfp4``): see
+:class:`InferenceStage`.
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ from ..utils.native import native
 from .. import switches
 
 
-WEIGHT_FORMATS = ("bf16", "fp8")
+WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
 FP8_GEMMS = ("scratch", "direct", "w8a8")
 
 
@@ -75,6 +77,17 @@ class InferenceStage:
     is untouched), so answers on the two sides of the 8/9-row line differ within the activation
     format's bound (2^-4 relative per element plus half a subnormal step of the row); for
     ``"direct"`` they do not.
+
+    ``weights="mxfp4"`` quantises each padded bf16 weight once with ``ops.quant_rows_mxfp4``
+    into ``self.q4[i]`` (uint8 [Np][Kp / 2], two e2m1 codes to a byte) and ``self.e4[i]`` (uint8
+    [Np][Kp / 32], one e8m0 scale per block of 32 columns) and does not keep the bf16 copy:
+    17/32 of a byte per weight resident. Requests of <= 8 rows run ``ops.gemv_mxfp4``, which
+    streams codes and scales in place. Larger buckets dequantise one layer at a time
+    (``ops.dequant_rows_mxfp4``) into the same bf16 scratch the fp8 path uses and run the bf16
+    GEMM on it; that dequantisation is exact (a code times a power of two is a bf16 value), so
+    such a bucket answers bit for bit as a bf16 stage loaded with the dequantised weights.
+    ``fp8_gemm`` is ignored. The format is coarse (per weight, the error is up to a quarter of
+    the weight or of the block's scale, whichever is larger), so it is opt-in.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
@@ -97,6 +110,7 @@ class InferenceStage:
         self.pads = [round_up(d, 64) for d in self.dims]
         self.w, self.b = [], []
         self.q, self.s = [], []  # fp8: codes and row scales
+        self.q4, self.e4 = [], []  # mxfp4: packed codes and block scales
         for L, kp, np_ in zip(self.layers, self.pads, self.pads[1:]):
             w = torch.zeros(np_, kp, dtype=torch.float32)
             w[:L.out_dim, :L.in_dim] = torch.as_tensor(np.asarray(L.weight, np.float32))
@@ -109,10 +123,17 @@ class InferenceStage:
                 ops.quant_rows_fp8(w, q, s)
                 self.q.append(q)
                 self.s.append(s)
+            elif weights == "mxfp4":
+                q = torch.empty(np_, kp // 2, dtype=torch.uint8, device=device)
+                e = torch.empty(np_, kp // 32, dtype=torch.uint8, device=device)
+                ops.quant_rows_mxfp4(w, q, e)
+                self.q4.append(q)
+                self.e4.append(e)
             else:
                 self.w.append(w)
             self.b.append(b.to(device))
-        self._wscratch: Optional[torch.Tensor] = None  # fp8, buckets > 8 rows: one bf16 layer
+        # fp8 / mxfp4, buckets > 8 rows: one bf16 layer
+        self._wscratch: Optional[torch.Tensor] = None
         self._bufs: dict[int, dict] = {}
 
     @property
@@ -127,12 +148,24 @@ class InferenceStage:
         """Layer i's weight operand for a kernel that reads the stage's weights in place (the
         device-side chain): ``(tensor, row stride, (Np, Kp), scale)``. bf16: the padded weight,
         its stride in elements, ``None``. fp8: the e4m3 codes, their stride in bytes, the fp32
-        row scales."""
+        row scales. An mxfp4 stage has no such operand: the device-side chain's kernels do not
+        read that format."""
+        if self.weights == "mxfp4":
+            raise ValueError(f"({self.name}) weight_operand: the device-side chain does not "
+                             "read mxfp4 weights (codes plus block scales); an mxfp4 stage "
+                             "serves on the host chain")
         if self.weights == "fp8":
             q = self.q[i]
             return q, q.stride(0), tuple(q.shape), self.s[i]
         w = self.w[i]
         return w, w.stride(0), tuple(w.shape), None
+
+    def resident_weight_bytes(self) -> int:
+        """Bytes of the weight operands this stage keeps resident (biases, buffers and the bf16
+        scratch of large buckets not counted). Per padded layer [Np][Kp]: bf16 2 Np Kp, fp8
+        Np Kp + 4 Np (codes and fp32 row scales), mxfp4 Np Kp / 2 + Np Kp / 32."""
+        return sum(t.numel() * t.element_size()
+                   for t in (*self.w, *self.q, *self.s, *self.q4, *self.e4))
 
     def check_input_dim(self, cols: int) -> None:
         """Dimension walk of grpc_node.py:80-93 against the configured widths."""
@@ -174,6 +207,17 @@ class InferenceStage:
         """y = act(x . W_i^T + b_i) from the stage's weight format."""
         if self.weights == "bf16":
             ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
+        elif self.weights == "mxfp4":
+            if x.shape[0] <= ops.GEMV_MAX_ROWS:
+                ops.gemv_mxfp4(x, self.q4[i], self.e4[i], self.b[i], y, act=act)
+                return
+            np_, kp = self.pads[i + 1], self.pads[i]
+            if self._wscratch is None:  # (first run of a bucket is eager: never under capture)
+                self._wscratch = torch.empty(max(a * b for a, b in zip(self.pads, self.pads[1:])),
+                                             dtype=torch.bfloat16, device=self.device)
+            w = self._wscratch[:np_ * kp].view(np_, kp)
+            ops.dequant_rows_mxfp4(self.q4[i], self.e4[i], w)
+            ops.linear_fwd(x, w, self.b[i], y, act=act)
         elif x.shape[0] <= ops.GEMV_MAX_ROWS:
             ops.gemv_fp8(x, self.q[i], self.s[i], self.b[i], y, act=act)
         elif self.fp8_gemm == "w8a8":
@@ -227,7 +271,7 @@ class InferenceEngine:
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch"):
-        """``weights``: "bf16" or "fp8", ``fp8_gemm``: "scratch", "direct" or "w8a8" (see
+        """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8" (see
         :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
@@ -253,6 +297,10 @@ class InferenceEngine:
     @property
     def input_dim(self) -> int:
         return self.stages[0].expected_input
+
+    def resident_weight_bytes(self) -> int:
+        """Sum of :meth:`InferenceStage.resident_weight_bytes` over the stages."""
+        return sum(st.resident_weight_bytes() for st in self.stages)
 
     def validate(self, cols: int) -> None:
         c = cols

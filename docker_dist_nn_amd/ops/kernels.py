@@ -469,6 +469,74 @@ def gemv_fp8(x, q, scale, bias, y, act="relu"):
     return y
 
 
+MXFP4_BLOCK = 32  # columns that share one e8m0 scale byte (csrc/kernels/mxfp4.hpp)
+
+
+def _mxfp4_operands(name, rows, cols, q, e):
+    if cols % MXFP4_BLOCK:
+        raise ValueError(f"{name} takes cols % {MXFP4_BLOCK} == 0")
+    _rows(q, "q", torch.uint8)
+    _rows(e, "e", torch.uint8)
+    if (q.shape[0] < rows or q.shape[1] < cols // 2 or e.shape[0] < rows
+            or e.shape[1] < cols // MXFP4_BLOCK):
+        raise ValueError(f"{name}: q must be uint8 [rows][>=cols/2], e uint8 [rows][>=cols/32]")
+
+
+def quant_rows_mxfp4(x, q, e):
+    """OCP MXFP4 weight rows: per block of 32 columns one e8m0 scale byte E and 32 e2m1 codes
+    (magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}, bit 3 the sign), column 2j in the low nibble of
+    byte j. Per block: amax < 2^-110 gives E = 0 and nibbles 0x0; otherwise E = floor(log2 amax)
+    - 2 + 127, t = x * 2^(127 - E) (exact), |t| > 6 saturates, else the nearest magnitude with a
+    tie to the even code; the sign bit is kept (tests/_mxfp4_oracle.py is the exact reference of
+    both paths). x bf16 [rows][cols], q uint8 [rows][>=cols/2], e uint8 [rows][>=cols/32];
+    cols % 32 == 0. Rows holding NaN or infinity are not specified."""
+    rows, cols = x.shape
+    _rows(x, "x", torch.bfloat16)
+    _mxfp4_operands("quant_rows_mxfp4", rows, cols, q, e)
+    if not x.is_cuda:
+        return ref.quant_rows_mxfp4(x, q, e)
+    native().quant_rows_mxfp4(_p(x), x.stride(0), rows, cols, _p(q), q.stride(0), _p(e),
+                              e.stride(0), _stream(x))
+
+
+def dequant_rows_mxfp4(q, e, x):
+    """Inverse of quant_rows_mxfp4 into bf16 x [rows][cols]: dec(code) * 2^(E - 127), exact
+    (no rounding) for every E the quantiser writes; a block with E == 0 gives +0."""
+    rows, cols = x.shape
+    _rows(x, "x", torch.bfloat16)
+    _mxfp4_operands("dequant_rows_mxfp4", rows, cols, q, e)
+    if not x.is_cuda:
+        return ref.dequant_rows_mxfp4(q, e, x)
+    native().dequant_rows_mxfp4(_p(q), q.stride(0), _p(e), e.stride(0), rows, cols, _p(x),
+                                x.stride(0), _stream(x))
+
+
+def gemv_mxfp4(x, q, e, bias, y, act="relu"):
+    """Serving-size layer (1..8 rows) over MXFP4 weight rows in the format of quant_rows_mxfp4:
+    y[m][n] = act(sum_k x[m][k] * e2m1(q[n][k]) * 2^(e[n][k / 32] - 127) + bias[n]), one wave per
+    output neuron, the block scale applied inside the hardware decode
+    (csrc/kernels/gemv_mxfp4.hip). x bf16 [M][K], q uint8 [N][>=K/2], e uint8 [N][>=K/32], y
+    bf16 or fp32; K % 32 == 0."""
+    M, K = x.shape
+    N = q.shape[0]
+    if M > GEMV_MAX_ROWS or K % MXFP4_BLOCK:
+        raise ValueError(f"gemv_mxfp4 takes <= {GEMV_MAX_ROWS} rows and K % {MXFP4_BLOCK} == 0")
+    _rows(x, "x", torch.bfloat16)
+    _mxfp4_operands("gemv_mxfp4", N, K, q, e)
+    if y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("gemv_mxfp4 operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not x.is_cuda:
+        return ref.gemv_mxfp4(x, q, e, bias, y, M, N, K, _act(act))
+    native().gemv_mxfp4(_p(x), x.stride(0), _p(q), q.stride(0), _p(e), e.stride(0), _p(bias),
+                        _p(y), y.stride(0), M, N, K, _act(act), int(y.dtype == torch.float32),
+                        _stream(x))
+    return y
+
+
 # Largest row bucket the serving engine runs on linear_fwd_fp8 under fp8_gemm="direct"; larger
 # buckets keep the dequantise-into-scratch path. Measured (bench/linear_fp8_bench.py,
 # profiles/linear_fp8/linear_fp8_bench.jsonl): the largest power-of-two bucket at which direct

@@ -97,6 +97,63 @@ def gemv_fp8(x, q, scale, bias, y, M, N, K, act):
     return y
 
 
+def e2m1_table() -> torch.Tensor:
+    """fp64 value of each of the 16 e2m1 codes s|ee|m: exponent 0 is subnormal (0, 0.5), else
+    (1 + m / 2) * 2^(ee - 1); bit 3 is the sign."""
+    c = torch.arange(16)
+    ee, m = (c >> 1) & 3, (c & 1).double()
+    v = torch.where(ee == 0, m * 0.5, (1.0 + m * 0.5) * torch.pow(2.0, (ee - 1).double()))
+    return torch.where(c >= 8, -v, v)
+
+
+_E2M1 = e2m1_table()
+MXFP4_TINY_EXP_FIELD = 17  # bf16 exponent field of 2^-110: blocks below it are zero blocks
+
+
+def quant_rows_mxfp4(x, q, e):
+    """The MXFP4 quantiser of csrc/kernels/mxfp4.hip on the bf16 bit fields and in fp64: E from
+    the exponent field of the block's largest magnitude, t = |x| * 2^(127 - E) (exact), the
+    code from the seven midpoints -- strict where the tie goes down to the even code, inclusive
+    where it goes up."""
+    rows, cols = x.shape
+    nb = cols // 32
+    bits = (x.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF).view(rows, nb, 32)
+    ef = (bits & 0x7FFF).amax(2) >> 7
+    send = ef >= MXFP4_TINY_EXP_FIELD
+    E = torch.where(send, ef - 2, torch.zeros_like(ef))
+    t = torch.ldexp(x.double().abs().view(rows, nb, 32), (127 - E)[:, :, None])
+    code = ((t > 0.25).int() + (t >= 0.75).int() + (t > 1.25).int() + (t >= 1.75).int()
+            + (t > 2.5).int() + (t >= 3.5).int() + (t > 5.0).int())
+    code = torch.where(send[:, :, None], code | ((bits >> 12) & 8), torch.zeros_like(code))
+    code = code.view(rows, cols)
+    q[:rows, :cols // 2] = (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+    e[:rows, :nb] = E.to(torch.uint8)
+
+
+def mxfp4_values(q, e, rows, cols) -> torch.Tensor:
+    """fp64 [rows][cols]: dec(code) * 2^(E - 127), +0 for a block with E == 0."""
+    b = q[:rows, :cols // 2].long()
+    code = torch.stack([b & 15, b >> 4], dim=2).view(rows, cols)
+    E = e[:rows, :cols // 32].long().repeat_interleave(32, dim=1)
+    v = torch.ldexp(_E2M1[code], E - 127)
+    return torch.where(E == 0, torch.zeros_like(v), v)
+
+
+def dequant_rows_mxfp4(q, e, x):
+    rows, cols = x.shape
+    x.copy_(mxfp4_values(q, e, rows, cols).to(torch.bfloat16))  # exact for every E >= 15
+
+
+def gemv_mxfp4(x, q, e, bias, y, M, N, K, act):
+    """y[:M, :N] = act(fl32(S) + bias), S = x . (dec(q) * 2^(e - 127))^T in fp64: the sum of the
+    kernel without its summation error, then the kernel's fp32 epilogue."""
+    v = (x[:M, :K].double() @ mxfp4_values(q, e, N, K).t()).float()
+    if bias is not None:
+        v = v + bias[:N].float()
+    y[:M, :N] = act_fwd(v, act).to(y.dtype)
+    return y
+
+
 def linear_w8a8(xq, sx, q, sw, bias, y, M, N, K, act):
     """y[:M, :N] = act(fl32(sx * fl32(sw * fl32(S))) + bias), S = dec(xq) . dec(q)^T in fp64: the
     sum of the kernel (csrc/kernels/linear_w8a8.hip) without its summation error, then the

@@ -435,6 +435,17 @@ class ChainRank:
                            self.out_pad)
 
 
+def fast_chain_veto(plan: dict) -> Optional[str]:
+    """Why a chain built from ``plan`` must not enable the device-side chain, or None. The
+    device-side chain's kernels read bf16 and fp8 weight operands
+    (``InferenceStage.weight_operand``); an mxfp4 stage has neither, so such a chain serves
+    every request on the host chain."""
+    if plan.get("weights", "bf16") == "mxfp4":
+        return ("host chain: the device-side chain does not read mxfp4 weights "
+                "(DNN_CHAIN_FAST ignored)")
+    return None
+
+
 def main(argv: Optional[list[str]] = None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--plan", required=True, help="JSON written by run_grpc_fcnn.py")
@@ -471,7 +482,9 @@ def main(argv: Optional[list[str]] = None) -> int:
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))
     if world > 1 and use_gpu and switches.get("DNN_CHAIN_FAST") == "1":
-        why = cr.enable_fast()
+        why = fast_chain_veto(plan)  # read from the plan: the same decision on every rank
+        if why is None:
+            why = cr.enable_fast()
         if rank == 0:
             log.info(f"({st['name']}) serving-size requests: {why}")
     log.info(f"({st['name']}) stage ready on {device}: {len(layers)} layer(s), "

@@ -10,10 +10,11 @@ The reference runs one container per stage whose behaviour is fixed by environme
   NEURONS_CONFIG      the stage's {"layer_1": [neurons...], ...} JSON inline, or
   NEURONS_FILE_CONFIG a path to it (the launcher's choice for configs > 1000 characters)
 
-and two entries of this project's: STAGE_WEIGHTS, "bf16" (default) or "fp8", the weight format
-of the stage's engine (run_grpc_fcnn.py --weights), and STAGE_FP8_GEMM, "scratch" (default),
+and two entries of this project's: STAGE_WEIGHTS, "bf16" (default), "fp8" or "mxfp4", the
+weight format of the stage's engine (run_grpc_fcnn.py --weights), and STAGE_FP8_GEMM, "scratch" (default),
 "direct" or "w8a8", how an fp8 stage runs buckets of more than 8 rows (--fp8-gemm; "w8a8" also
-quantises each layer's activations to e4m3). The value is passed to the engine unchanged.
+quantises each layer's activations to e4m3; ignored by an mxfp4 stage). The values are passed to
+the engine unchanged.
 
 This worker keeps that contract, the LayerService protocol and the error mapping of
 grpc_node.py:99-158 (ValueError -> INVALID_ARGUMENT, a failed forward keeps the downstream
