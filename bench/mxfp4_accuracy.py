@@ -4,7 +4,9 @@ same model and the same inputs. The model is the mnist-fcnn MLP (784-512-256-128
 ``--steps`` SGD steps on the synthetic teacher-labelled MNIST-shaped set (data.synthetic_mnist,
 what ``run_grpc_inference.py --local`` is pointed at when no real data is present); the inputs
 are ``--rows`` held-out rows of that set, sent in requests of 8 rows (the GEMV path, which reads
-the codes in place) and as one batch (the large-bucket path). The last layer is served as
+the codes in place) and as one batch (the large-bucket path); the mxfp4 engine with
+``mxfp4_gemm="w4a8"`` (fp8 activations against the codes) is one more contender, in requests of
+64 rows. The last layer is served as
 ``linear`` so that logits, not probabilities, are compared. One JSON line."""
 from __future__ import annotations
 
@@ -44,6 +46,7 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--rows", type=int, default=2048)
+    ap.add_argument("--out", type=str, default="", help="also append the line to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mxfp4_accuracy needs a GPU: the engines under test run there")
@@ -63,6 +66,17 @@ def main() -> int:
         logits[fmt] = {"rows8": small, "batch": eng.predict(x)}
         out[f"{fmt}_resident_weight_bytes"] = eng.resident_weight_bytes()
         out[f"{fmt}_top1_vs_labels"] = round(float((small.argmax(1) == labels).mean()), 4)
+    # mxfp4 codes against fp8 activations (--mxfp4-gemm w4a8), in requests of 64 rows: the bucket
+    # its MFMA path serves; against the bf16 engine on the same requests
+    rows64 = {}
+    for name, kw in (("bf16", {}), ("mxfp4_w4a8", {"weights": "mxfp4", "mxfp4_gemm": "w4a8"})):
+        eng = InferenceEngine([layers], dev, expected_input=784, **kw)
+        rows64[name] = np.concatenate([eng.predict(x[k:k + 64]) for k in range(0, a.rows, 64)])
+    got, want = rows64["mxfp4_w4a8"], rows64["bf16"]
+    out["mxfp4_w4a8_top1_vs_labels"] = round(float((got.argmax(1) == labels).mean()), 4)
+    out["mxfp4_w4a8_rows64_top1_agreement"] = round(
+        float((got.argmax(1) == want.argmax(1)).mean()), 4)
+    out["mxfp4_w4a8_rows64_mean_abs_logit_diff"] = round(float(np.abs(got - want).mean()), 5)
     out["bf16_mean_abs_logit"] = round(float(np.abs(logits["bf16"]["rows8"]).mean()), 4)
     for fmt in ("fp8", "mxfp4"):
         for path in ("rows8", "batch"):
@@ -71,6 +85,10 @@ def main() -> int:
                 float((got.argmax(1) == want.argmax(1)).mean()), 4)
             out[f"{fmt}_{path}_mean_abs_logit_diff"] = round(float(np.abs(got - want).mean()), 5)
     print(json.dumps(out), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(json.dumps(out) + "\n")
     return 0
 
 

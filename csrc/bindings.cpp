@@ -24,6 +24,7 @@
 #include "kernels/gemv_fp8.hpp"
 #include "kernels/gemv_mxfp4.hpp"
 #include "kernels/linear_fp8.hpp"
+#include "kernels/linear_w4a8.hpp"
 #include "kernels/linear_w8a8.hpp"
 #include "kernels/mlp_tail.hpp"
 #include "kernels/mxfp4.hpp"
@@ -257,6 +258,27 @@ PYBIND11_MODULE(_native, m) {
       py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("act"), py::arg("out_f32"), py::arg("stream"), py::arg("tile") = 0);
   m.def("linear_w8a8_tiles", []() { return dnn::LINEAR_W8A8_TILES; });
+  m.def(
+      "linear_w4a8",
+      [](uintptr_t xq, long ldxq, uintptr_t sx, uintptr_t q, long ldq, uintptr_t e, long lde,
+         uintptr_t bias, uintptr_t y, long ldy, int M, int N, int K, int act, int out_f32,
+         uintptr_t stream, int tile) {
+        launch(
+            "linear_w4a8",
+            [=](hipStream_t s, const dnn::Program& R) {
+              return dnn::linear_w4a8(R.fix(P<const unsigned char>(xq)), ldxq,
+                                      R.fix(P<const float>(sx)),
+                                      R.fix(P<const unsigned char>(q)), ldq,
+                                      R.fix(P<const unsigned char>(e)), lde,
+                                      R.fix(P<const float>(bias)), R.fix(P<void>(y)), ldy, M, N, K,
+                                      act, out_f32, tile, s);
+            },
+            stream);
+      },
+      py::arg("xq"), py::arg("ldxq"), py::arg("sx"), py::arg("q"), py::arg("ldq"), py::arg("e"),
+      py::arg("lde"), py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"),
+      py::arg("K"), py::arg("act"), py::arg("out_f32"), py::arg("stream"), py::arg("tile") = 0);
+  m.def("linear_w4a8_tiles", []() { return dnn::LINEAR_W4A8_TILES; });
   m.def(
       "gemm_bf16_streamk",
       [](uintptr_t a, long lda, uintptr_t b, long ldb, uintptr_t c, long ldc, int M, int N, int K,

@@ -59,6 +59,12 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "GEMM on the codes, up to ops.FP8_DIRECT_MAX_ROWS rows; w8a8 = also "
                          "quantises the activations of every layer to e4m3 (one scale per row) "
                          "and multiplies codes by codes on the fp8 MFMA, at any number of rows")
+    ap.add_argument("--mxfp4-gemm", choices=["scratch", "w4a8"], default="scratch",
+                    help="with --weights mxfp4, buckets of more than 8 rows: scratch = dequantise "
+                         "the layer into a bf16 buffer + the bf16 GEMM; w4a8 = quantises the "
+                         "activations of every layer to e4m3 (one scale per row) and multiplies "
+                         "the 4-bit codes by them on the block-scaled MFMA, the e8m0 block scales "
+                         "as its scale operand, at any number of rows")
     ap.add_argument("--port", type=int, default=5101)
     ap.add_argument("--layer-distribution", type=str, default=None,
                     help="override, e.g. '[1,1,1]'")
@@ -280,7 +286,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             dev = _device(a.device)
             eng = InferenceEngine([mc.layers[p.layer_start:p.layer_end] for p in plans], dev,
                                   expected_input=input_dim, names=[s["name"] for s in stage_entries],
-                                  weights=a.weights, fp8_gemm=a.fp8_gemm)
+                                  weights=a.weights, fp8_gemm=a.fp8_gemm,
+                                  mxfp4_gemm=a.mxfp4_gemm)
             server = serve(eng.predict, port=a.port, name=stage_entries[0]["name"])
         elif mode == "workers":
             from ..launch import spawn_workers, wait_for_port
@@ -304,6 +311,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                 e["DNN_WORKER_DEVICE"] = "cpu" if a.device == "cpu" else "auto"
                 e["STAGE_WEIGHTS"] = a.weights
                 e["STAGE_FP8_GEMM"] = a.fp8_gemm
+                e["STAGE_MXFP4_GEMM"] = a.mxfp4_gemm
                 e["LOCAL_RANK"] = str(k)
                 stage_envs.append(e)
             job = spawn_workers("docker_dist_nn_amd.serve.worker", stage_envs,
@@ -319,7 +327,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             plan_path = os.path.join(a.cache_dir, "chain_plan.json")
             json.dump({"stages": stage_entries, "port": a.port, "hop_timeout": a.hop_timeout,
                        "device": "cpu" if a.device == "cpu" else "auto",
-                       "weights": a.weights, "fp8_gemm": a.fp8_gemm}, open(plan_path, "w"))
+                       "weights": a.weights, "fp8_gemm": a.fp8_gemm,
+                       "mxfp4_gemm": a.mxfp4_gemm}, open(plan_path, "w"))
             job = spawn_ranks("docker_dist_nn_amd.serve.chain", ["--plan", plan_path], n_st,
                               devices=list(range(n_st)) if a.device != "cpu" else None,
                               names=[s["name"] for s in stage_entries])

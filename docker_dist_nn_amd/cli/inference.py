@@ -47,6 +47,10 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --local --weights fp8: how buckets of more than 8 rows run "
                          "(InferenceStage); w8a8 also quantises the activations to e4m3")
+    ap.add_argument("--mxfp4-gemm", choices=["scratch", "w4a8"], default="scratch",
+                    help="with --local --weights mxfp4: how buckets of more than 8 rows run "
+                         "(InferenceStage); w4a8 quantises the activations to e4m3 and runs the "
+                         "4-bit codes on the block-scaled MFMA")
     ap.add_argument("--metrics-json", type=str, default=None)
     return ap
 
@@ -87,7 +91,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
         dev = torch.device("cpu") if a.device == "cpu" or not torch.cuda.is_available() \
             else torch.device("cuda", 0)
         eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
-                              weights=a.weights, fp8_gemm=a.fp8_gemm)
+                              weights=a.weights, fp8_gemm=a.fp8_gemm,
+                              mxfp4_gemm=a.mxfp4_gemm)
 
         def call(batch):
             return eng.predict(batch)

@@ -36,6 +36,7 @@ from .. import switches
 
 WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
 FP8_GEMMS = ("scratch", "direct", "w8a8")
+MXFP4_GEMMS = ("scratch", "w4a8")
 
 
 class InferenceStage:
@@ -88,18 +89,34 @@ class InferenceStage:
     such a bucket answers bit for bit as a bf16 stage loaded with the dequantised weights.
     ``fp8_gemm`` is ignored. The format is coarse (per weight, the error is up to a quarter of
     the weight or of the block's scale, whichever is larger), so it is opt-in.
+
+    ``mxfp4_gemm="w4a8"`` (with ``weights="mxfp4"``; ignored with bf16 and fp8, as ``fp8_gemm`` is
+    ignored by an mxfp4 stage) serves every bucket of more than ``ops.GEMV_MAX_ROWS`` rows, with
+    no row cap, straight from the codes: each layer is ``ops.quant_rows_fp8`` of its input buffer
+    followed by ``ops.linear_w4a8``, which multiplies the e2m1 codes by the e4m3 codes on the
+    block-scaled MFMA with the e8m0 block scales as the instruction's own scale operand. The
+    code and scale buffers of every layer live in ``buffers(rows)`` exactly as w8a8's do, so
+    graph capture and native replay stay valid, and such a stage never allocates the bf16
+    scratch. Requests of <= 8 rows keep ``ops.gemv_mxfp4`` on bf16 activations, so answers on
+    the two sides of the 8/9-row line differ within the activation format's bound (2^-4
+    relative per element plus half a subnormal step of the row); under ``"scratch"`` (the
+    default) they do not. ``weight_operand`` still raises and an mxfp4 rank chain still serves on
+    the host chain.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
                  expected_input: int, name: str = "layer", is_last: bool = True,
                  case_sensitive: bool = True, weights: str = "bf16",
-                 fp8_gemm: str = "scratch"):
+                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch"):
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
         if fp8_gemm not in FP8_GEMMS:
             raise ValueError(f"fp8_gemm must be one of {FP8_GEMMS}, got {fp8_gemm!r}")
+        if mxfp4_gemm not in MXFP4_GEMMS:
+            raise ValueError(f"mxfp4_gemm must be one of {MXFP4_GEMMS}, got {mxfp4_gemm!r}")
         self.weights = weights
         self.fp8_gemm = fp8_gemm
+        self.mxfp4_gemm = mxfp4_gemm
         self.device = device
         self.name = name
         self.is_last = is_last
@@ -185,7 +202,8 @@ class InferenceStage:
             dev = self.device
             b = {"x": torch.zeros(rows, self.pads[0], dtype=torch.bfloat16, device=dev),
                  "h": [], "f32": [], "xq": [], "sx": []}
-            if self._w8a8(rows):  # every layer's input as e4m3 codes + one fp32 scale per row
+            # w8a8 / w4a8: every layer's input as e4m3 codes + one fp32 scale per row
+            if self._w8a8(rows) or self._w4a8(rows):
                 for kp in self.pads[:-1]:
                     b["xq"].append(torch.zeros(rows, kp, dtype=torch.uint8, device=dev))
                     b["sx"].append(torch.zeros(rows, dtype=torch.float32, device=dev))
@@ -203,6 +221,11 @@ class InferenceStage:
         return (self.weights == "fp8" and self.fp8_gemm == "w8a8"
                 and rows > ops.GEMV_MAX_ROWS)
 
+    def _w4a8(self, rows: int) -> bool:
+        """Whether a bucket of ``rows`` rows runs the mxfp4 codes against fp8 activations."""
+        return (self.weights == "mxfp4" and self.mxfp4_gemm == "w4a8"
+                and rows > ops.GEMV_MAX_ROWS)
+
     def _linear(self, i: int, x: torch.Tensor, y: torch.Tensor, act: str) -> None:
         """y = act(x . W_i^T + b_i) from the stage's weight format."""
         if self.weights == "bf16":
@@ -210,6 +233,11 @@ class InferenceStage:
         elif self.weights == "mxfp4":
             if x.shape[0] <= ops.GEMV_MAX_ROWS:
                 ops.gemv_mxfp4(x, self.q4[i], self.e4[i], self.b[i], y, act=act)
+                return
+            if self.mxfp4_gemm == "w4a8":
+                b = self.buffers(x.shape[0])
+                ops.linear_fwd_w4a8(x, self.q4[i], self.e4[i], self.b[i], y, act=act,
+                                    xq=b["xq"][i], sx=b["sx"][i])
                 return
             np_, kp = self.pads[i + 1], self.pads[i]
             if self._wscratch is None:  # (first run of a bucket is eager: never under capture)
@@ -270,9 +298,9 @@ class InferenceEngine:
     def __init__(self, stage_layers: Sequence[Sequence[LayerWeights]], device: torch.device,
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
-                 fp8_gemm: str = "scratch"):
-        """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8" (see
-        :class:`InferenceStage`), for every stage."""
+                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch"):
+        """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8",
+        ``mxfp4_gemm``: "scratch" or "w4a8" (see :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
@@ -280,7 +308,7 @@ class InferenceEngine:
         for i, ls in enumerate(stage_layers):
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
                                 is_last=i == len(stage_layers) - 1, weights=weights,
-                                fp8_gemm=fp8_gemm)
+                                fp8_gemm=fp8_gemm, mxfp4_gemm=mxfp4_gemm)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

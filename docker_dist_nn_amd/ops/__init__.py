@@ -7,6 +7,7 @@ from .kernels import (FP8_DIRECT_MAX_ROWS, FP8_MAX, FP8_TINY_AMAX, MXFP4_BLOCK, 
                       dense_loss_row_blocks, check_dense_loss, dequant_rows_fp8, quant_rows_fp8,
                       dequant_rows_mxfp4, quant_rows_mxfp4, gemv_mxfp4,
                       gemm, gemv, gemv_fp8, linear_dgrad, linear_fwd, linear_fwd_fp8, linear_fwd_w8a8, linear_fwd_xent, linear_w8a8,
+                      linear_fwd_w4a8, linear_w4a8, W4A8_TILES,
                       linear_wgrad, linear_wgrad_group, linear_wgrad_streamk, mlp_tail, pack_bf16,
                       reduce_multi, reduce_slabs, sgd_update, softmax_rows, softmax_xent,
                       step_advance, streamk_partial_elems, streamk_tiles, tail_blocks,
@@ -19,6 +20,7 @@ __all__ = ["FP8_DIRECT_MAX_ROWS", "FP8_MAX", "FP8_TINY_AMAX", "MXFP4_BLOCK", "GE
            "dense_loss_row_blocks", "check_dense_loss", "dequant_rows_fp8", "quant_rows_fp8",
            "dequant_rows_mxfp4", "quant_rows_mxfp4", "gemv_mxfp4",
            "dgrad_tiles", "gemm", "gemv", "gemv_fp8", "linear_dgrad", "linear_fwd", "linear_fwd_fp8", "linear_fwd_w8a8", "linear_fwd_xent", "linear_w8a8",
+           "linear_fwd_w4a8", "linear_w4a8", "W4A8_TILES",
            "linear_wgrad", "linear_wgrad_group", "linear_wgrad_streamk", "mlp_tail", "pack_bf16", "pick_splits", "pick_tiles",
            "reduce_multi", "reduce_slabs", "sgd_update", "softmax_rows", "softmax_xent",
            "step_advance", "streamk_partial_elems", "streamk_tiles", "tail_blocks", "tail_supported",

@@ -628,6 +628,66 @@ def linear_fwd_w8a8(x, q, scale, bias, y, act="relu", xq=None, sx=None, tile=0):
     return linear_w8a8(xq[:M, :K], sx, q, scale, bias, y, act, tile)
 
 
+W4A8_TILES = 2  # csrc/kernels/linear_w4a8.hpp LINEAR_W4A8_TILES (asserted on the GPU path)
+
+
+def linear_w4a8(xq, sx, q, e, bias, y, act="relu", tile=0):
+    """Forward layer over MXFP4 weight rows (quant_rows_mxfp4) against e4m3 activation rows
+    (quant_rows_fp8): y[m][n] = act(fl32(sx[m] * sum_k e4m3(xq[m][k]) * e2m1(q[n][k]) *
+    2^(e[n][k / 32] - 127)) + bias[n]) on the block-scaled MFMA in its fp4 x fp8 form
+    (csrc/kernels/linear_w4a8.hip): the block scales are the instruction's scale operand, the
+    row scale one rounded fp32 multiply in the epilogue; a block with scale byte 0 contributes
+    nothing. xq uint8 [M][>=K] codes of the rows, sx fp32 [>=M], q uint8 [N][>=K/2], e uint8
+    [N][>=K/32] (any alignment), y bf16 or fp32; K % 32 == 0, rows of xq and q 16-byte aligned,
+    any M >= 1.
+    ``tile``: 0 = chosen by the launcher, 1 / 2 force one (linear_w4a8.hpp; tests, benchmark)."""
+    M, K = xq.shape
+    N = q.shape[0]
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"linear_w4a8 takes K % {MXFP4_BLOCK} == 0")
+    _rows(xq, "xq", torch.uint8)
+    _mxfp4_operands("linear_w4a8", N, K, q, e)
+    if y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("linear_w4a8 operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if sx.dtype != torch.float32 or sx.numel() < M or not sx.is_contiguous():
+        raise ValueError("sx must be contiguous fp32 with >= M entries")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not 0 <= int(tile) <= W4A8_TILES:
+        raise ValueError(f"linear_w4a8 tile must be 0..{W4A8_TILES}")
+    if not xq.is_cuda:
+        return ref.linear_w4a8(xq, sx, q, e, bias, y, M, N, K, _act(act))
+    assert native().linear_w4a8_tiles() == W4A8_TILES
+    for name, t in (("xq", xq), ("q", q)):
+        if t.data_ptr() % 16 or t.stride(0) % 16:
+            raise ValueError(f"linear_w4a8: rows of {name} must be 16-byte aligned")
+    native().linear_w4a8(_p(xq), xq.stride(0), _p(sx), _p(q), q.stride(0), _p(e), e.stride(0),
+                         _p(bias), _p(y), y.stride(0), M, N, K, _act(act),
+                         int(y.dtype == torch.float32), _stream(xq), int(tile))
+    return y
+
+
+def linear_fwd_w4a8(x, q, e, bias, y, act="relu", xq=None, sx=None, tile=0):
+    """A layer served from MXFP4 weights with fp8 activations: quant_rows_fp8(x) into ``xq`` /
+    ``sx`` (uint8 [>=M][>=K] with 16-byte aligned rows and fp32 [>=M]; temporaries when not
+    given), then linear_w4a8 on them. x bf16 [M][K]; everything else as linear_w4a8. Every
+    column of x enters its row's amax, so the answer differs from gemv_mxfp4's within the
+    activation format's bound (tests/_fp8_oracle.round_trip_bound) unless the quantiser loses
+    nothing."""
+    M, K = x.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"linear_fwd_w4a8 takes K % {MXFP4_BLOCK} == 0")
+    _rows(x, "x", torch.bfloat16)
+    if xq is None:
+        xq = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    if sx is None:
+        sx = torch.empty(M, dtype=torch.float32, device=x.device)
+    quant_rows_fp8(x, xq, sx)
+    return linear_w4a8(xq[:M, :K], sx, q, e, bias, y, act, tile)
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

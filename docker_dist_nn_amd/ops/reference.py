@@ -167,6 +167,19 @@ def linear_w8a8(xq, sx, q, sw, bias, y, M, N, K, act):
     return y
 
 
+def linear_w4a8(xq, sx, q, e, bias, y, M, N, K, act):
+    """y[:M, :N] = act(fl32(sx * fl32(S)) + bias), S = dec(xq) . (dec(q) * 2^(e - 127))^T in
+    fp64 with E == 0 blocks +0: the sum of the kernel (csrc/kernels/linear_w4a8.hip) without its
+    summation error, then the kernel's fp32 epilogue -- the row scale one multiply rounded on
+    its own."""
+    S = _E4M3[xq[:M, :K].long()] @ mxfp4_values(q, e, N, K).t()
+    v = sx[:M].float()[:, None] * S.float()
+    if bias is not None:
+        v = v + bias[:N].float()
+    y[:M, :N] = act_fwd(v, act).to(y.dtype)
+    return y
+
+
 def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
                  rows_per_block=64, colsum=None):
     rows, width = dz.shape

@@ -478,7 +478,8 @@ def main(argv: Optional[list[str]] = None) -> int:
     names = [s["name"] for s in plan["stages"]]
     stage = InferenceStage(layers, device, expected_input=st["expected_input"], name=st["name"],
                            is_last=rank == world - 1, weights=plan.get("weights", "bf16"),
-                           fp8_gemm=plan.get("fp8_gemm", "scratch"))
+                           fp8_gemm=plan.get("fp8_gemm", "scratch"),
+                           mxfp4_gemm=plan.get("mxfp4_gemm", "scratch"))
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))
     if world > 1 and use_gpu and switches.get("DNN_CHAIN_FAST") == "1":

@@ -10,11 +10,13 @@ The reference runs one container per stage whose behaviour is fixed by environme
   NEURONS_CONFIG      the stage's {"layer_1": [neurons...], ...} JSON inline, or
   NEURONS_FILE_CONFIG a path to it (the launcher's choice for configs > 1000 characters)
 
-and two entries of this project's: STAGE_WEIGHTS, "bf16" (default), "fp8" or "mxfp4", the
+and three entries of this project's: STAGE_WEIGHTS, "bf16" (default), "fp8" or "mxfp4", the
 weight format of the stage's engine (run_grpc_fcnn.py --weights), and STAGE_FP8_GEMM, "scratch" (default),
 "direct" or "w8a8", how an fp8 stage runs buckets of more than 8 rows (--fp8-gemm; "w8a8" also
-quantises each layer's activations to e4m3; ignored by an mxfp4 stage). The values are passed to
-the engine unchanged.
+quantises each layer's activations to e4m3; ignored by an mxfp4 stage), and STAGE_MXFP4_GEMM,
+"scratch" (default) or "w4a8", how an mxfp4 stage runs those buckets (--mxfp4-gemm; "w4a8" runs
+the 4-bit codes against e4m3 activations; ignored by bf16 and fp8 stages). The values are passed
+to the engine unchanged.
 
 This worker keeps that contract, the LayerService protocol and the error mapping of
 grpc_node.py:99-158 (ValueError -> INVALID_ARGUMENT, a failed forward keeps the downstream
@@ -79,7 +81,8 @@ class StageWorker:
         return InferenceEngine([self.layers], dev, expected_input=self.expected_input_dim,
                                names=[self.container_name],
                                weights=env.get("STAGE_WEIGHTS", "bf16") or "bf16",
-                               fp8_gemm=env.get("STAGE_FP8_GEMM", "scratch") or "scratch")
+                               fp8_gemm=env.get("STAGE_FP8_GEMM", "scratch") or "scratch",
+                               mxfp4_gemm=env.get("STAGE_MXFP4_GEMM", "scratch") or "scratch")
 
     def _client(self):
         from .ingress import LayerClient
