@@ -8,10 +8,12 @@ through host memory over gloo (``rehearsal``: DNN_FORCE_DEVICE=0, DNN_DIST_BACKE
 8-GPU node each stage has its own GPU and the hops are RCCL. One JSON line.
 
 ``--weights fp8`` serves from e4m3 weight codes (run_grpc_fcnn.py --weights): on the device-side
-chain by default, on the host chain with DNN_CHAIN_FAST=0 in the environment.
+chain by default, on the host chain with DNN_CHAIN_FAST=0 in the environment. ``--weights mxfp4``
+serves from e2m1 codes and e8m0 block scales: on the host chain unless ``--mxfp4-chain device``
+is given too (run_grpc_fcnn.py --mxfp4-chain).
 
 Usage: python bench/chain_latency.py [--iters 500] [--rows 1] [--stages 8] [--width 1024]
-                                     [--weights {bf16,fp8}]"""
+                                     [--weights {bf16,fp8,mxfp4}] [--mxfp4-chain {host,device}]"""
 from __future__ import annotations
 
 import argparse
@@ -34,8 +36,11 @@ def main():
     ap.add_argument("--rows", type=int, default=1)
     ap.add_argument("--stages", type=int, default=8)
     ap.add_argument("--width", type=int, default=1024)
-    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
+    ap.add_argument("--weights", choices=("bf16", "fp8", "mxfp4"), default="bf16",
                     help="the stages' resident weight format (run_grpc_fcnn.py --weights)")
+    ap.add_argument("--mxfp4-chain", choices=("host", "device"), default="host",
+                    help="with --weights mxfp4: the chain that serves the requests "
+                         "(run_grpc_fcnn.py --mxfp4-chain)")
     ap.add_argument("--log", default=None, help="write the servers' log here")
     a = ap.parse_args()
     import torch
@@ -71,7 +76,7 @@ def main():
                               "--config", cfg, "--inputs", inp, "--port", str(port),
                               "--mode", "ranks", "--device", "cuda" if n_gpu else "cpu",
                               "--cache-dir", os.path.join(d, "cache"), "--run-for", "600",
-                              "--weights", a.weights],
+                              "--weights", a.weights, "--mxfp4-chain", a.mxfp4_chain],
                              env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         ok = True
         try:
@@ -105,7 +110,9 @@ def main():
                     f.write(log or "")
             if not ok:
                 print((log or "")[-6000:], file=sys.stderr, flush=True)
-    fast = "device-side chain" in (log or "")
+    # the enable message of serve/fastpath.py (an mxfp4 chain's host-chain reason names the
+    # device-side chain too)
+    fast = "device-side chain (" in (log or "")
     import re
     m = re.search(r"(device-side|message) chain predict latency over (\d+) requests: "
                   r"p50 ([\d.]+) ms p90 ([\d.]+) ms p99 ([\d.]+) ms", log or "")
@@ -116,6 +123,7 @@ def main():
     print(json.dumps({"metric": "inference chain latency", "path": "rank chain (grpc ingress)",
                       "stages": a.stages, "rows": a.rows, "model": "-".join(map(str, dims)),
                       "weights": a.weights,
+                      "mxfp4_chain": a.mxfp4_chain if a.weights == "mxfp4" else None,
                       "transport": ("device-side chain: IPC slots + flags (serve/fastpath.py)"
                                     if fast else "gloo via host" if rehearsal else "rccl") +
                                    (", one-GPU rehearsal: every stage on cuda:0"

@@ -1249,10 +1249,13 @@ PYBIND11_MODULE(_native, m) {
           int rows, int N, int K, int out_f32, uintptr_t dst, long dst_ld, uintptr_t dst_hdr,
           uintptr_t in_hdr, uintptr_t err, int stage, uint32_t status, uintptr_t ack,
           uint32_t ack_target, uintptr_t next_flag, uint32_t seq, uintptr_t prev_ack,
-          uintptr_t counter, double timeout_s, uintptr_t in_flag, uintptr_t w_scale) {
+          uintptr_t counter, double timeout_s, uintptr_t in_flag, uintptr_t w_scale,
+          uintptr_t w_e8m0, long lde) {
         dnn::ChainGemvSend p{};
         p.in_flag = static_cast<const uint32_t*>(ptr(in_flag));
         p.w_scale = static_cast<const float*>(ptr(w_scale));  // != 0: w holds e4m3 codes
+        p.w_e8m0 = static_cast<const unsigned char*>(ptr(w_e8m0));  // != 0: w holds e2m1 codes
+        p.lde = lde;
         p.x = static_cast<const uint16_t*>(ptr(x));
         p.ldx = ldx;
         p.w = static_cast<const uint16_t*>(ptr(w));
@@ -1285,7 +1288,7 @@ PYBIND11_MODULE(_native, m) {
       py::arg("in_hdr"), py::arg("err"), py::arg("stage"), py::arg("status"), py::arg("ack"),
       py::arg("ack_target"), py::arg("next_flag"), py::arg("seq"), py::arg("prev_ack"),
       py::arg("counter"), py::arg("timeout_s"), py::arg("in_flag") = 0,
-      py::arg("w_scale") = 0);
+      py::arg("w_scale") = 0, py::arg("w_e8m0") = 0, py::arg("lde") = 0);
   py::class_<dnn::ChainHost>(m, "ChainHost",
                              "rank 0's native request path of the device-side chain "
                              "(runtime/chain_host.hpp)")
@@ -1298,7 +1301,8 @@ PYBIND11_MODULE(_native, m) {
               uintptr_t dst_hdr, uintptr_t err, uintptr_t ack, uint32_t ack_target,
               uintptr_t next_flag, uint32_t seq, uintptr_t counter, double hop_timeout_s,
               uintptr_t res_flag, uintptr_t res_err, uintptr_t res_dev, uintptr_t res_host,
-              size_t res_bytes, uintptr_t last_ack, double wait_timeout_s, uintptr_t w_scale) {
+              size_t res_bytes, uintptr_t last_ack, double wait_timeout_s, uintptr_t w_scale,
+              uintptr_t w_e8m0, long lde) {
             dnn::ChainRequest r{};
             r.stream = S(stream);
             r.res_stream = S(res_stream);
@@ -1311,6 +1315,8 @@ PYBIND11_MODULE(_native, m) {
             p.w = static_cast<const uint16_t*>(ptr(w));
             p.ldw = ldw;
             p.w_scale = static_cast<const float*>(ptr(w_scale));
+            p.w_e8m0 = static_cast<const unsigned char*>(ptr(w_e8m0));
+            p.lde = lde;
             p.bias = static_cast<const float*>(ptr(bias));
             p.act = act;
             p.rows = rows;
@@ -1342,7 +1348,8 @@ PYBIND11_MODULE(_native, m) {
           py::arg("ack_target"), py::arg("next_flag"), py::arg("seq"), py::arg("counter"),
           py::arg("hop_timeout_s"), py::arg("res_flag"), py::arg("res_err"), py::arg("res_dev"),
           py::arg("res_host"), py::arg("res_bytes"), py::arg("last_ack"),
-          py::arg("wait_timeout_s"), py::arg("w_scale") = 0)
+          py::arg("wait_timeout_s"), py::arg("w_scale") = 0, py::arg("w_e8m0") = 0,
+          py::arg("lde") = 0)
       .def(
           "wait",
           [](dnn::ChainHost& h, int slot, double timeout_s) {
@@ -1360,9 +1367,11 @@ PYBIND11_MODULE(_native, m) {
           long hdr_stride, uintptr_t next_flags, uintptr_t ack, uintptr_t stop, uintptr_t done,
           uintptr_t sync, uint32_t start_seq, uint32_t epoch, int stage, int nslot,
           int max_rows, double idle_s, double timeout_s, int workgroups, int share,
-          uintptr_t w_scale) {
+          uintptr_t w_scale, uintptr_t w_e8m0, long lde) {
         dnn::ChainStage p{};
         p.w_scale = static_cast<const float*>(ptr(w_scale));  // != 0: w holds e4m3 codes
+        p.w_e8m0 = static_cast<const unsigned char*>(ptr(w_e8m0));  // != 0: w holds e2m1 codes
+        p.lde = lde;
         p.in_flags = static_cast<const uint32_t*>(ptr(in_flags));
         p.in_hdrs = static_cast<const uint32_t*>(ptr(in_hdrs));
         p.in_slots = static_cast<const uint16_t*>(ptr(in_slots));
@@ -1404,7 +1413,7 @@ PYBIND11_MODULE(_native, m) {
       py::arg("next_flags"), py::arg("ack"), py::arg("stop"), py::arg("done"), py::arg("sync"),
       py::arg("start_seq"), py::arg("epoch"), py::arg("stage"), py::arg("nslot"),
       py::arg("max_rows"), py::arg("idle_s"), py::arg("timeout_s"), py::arg("workgroups") = 0,
-      py::arg("share") = 1, py::arg("w_scale") = 0);
+      py::arg("share") = 1, py::arg("w_scale") = 0, py::arg("w_e8m0") = 0, py::arg("lde") = 0);
   m.def(
       "chain_signal",
       [=](uintptr_t s, uintptr_t flag, uint32_t value) {

@@ -12,13 +12,38 @@
 //                                         2          1   4    124        4
 //                                         4          1   2    122        4
 //                                         8          1   2    202        2
-//   chain_stage_kernel<true>              1          4   4    242        2
+//   chain_stage_kernel<1>                 1          4   4    242        2
 //   (one kernel holds all four            2          4   4   (the whole kernel)
 //   cs_layer_fp8 forms)                   4          4   2
 //                                         8          4   2
 // (NB: neurons a wave holds at once; U: 1024-column chunks whose loads are in flight together.
 // The stage kernel reads x from LDS 8 columns at a time: with a lane's 16 columns of 8 rows
 // held at once it needed 256 VGPRs + 20 AGPRs and ran at 1 wave/SIMD.)
+//
+// Or (w_e8m0 != nullptr) MXFP4: packed e2m1 codes with one e8m0 scale byte per 32 columns, summed
+// in gemv_mxfp4.hip's order so the rows are bitwise that kernel's. That order depends on the
+// lane's unit (16 or 32 columns), so both exist; the unit is chosen as gemv_mxfp4 chooses it.
+// Registers of the mxfp4 forms (same build, same remark; none has scratch; the bf16 and fp8
+// forms above are unchanged):
+//   kernel                          rows capacity   unit   NB   U   VGPRs   waves/SIMD
+//   chain_gemv_send_kernel<.,.,0,B>       1          32     1   2     78        6
+//                                         2          32     1   2    124        4
+//                                         1          16     1   4     94        5
+//                                         2          16     1   4    136        3
+//                                         4          16     1   2    128        4
+//                                         8          16     1   2    208        2
+//   chain_stage_kernel<2>                 1          32     4   2    256        2
+//   (one kernel holds all six             2          32     4   2   (the whole kernel)
+//   cs_layer_mxfp4 forms)                 1          16     4   4
+//                                         2          16     4   4
+//                                         4          16     4   2
+//                                         8          16     4   1
+// (unit: columns of a lane per chunk of 64 units; 32 serves 1 and 2 rows when K >= 2048. Alone,
+// the six stage forms take 136 / 169 / 168 / 192 / 174 / 200 VGPRs; with U = 2 at 8 rows (226
+// alone) the whole kernel came to 256 VGPRs + 12 AGPRs, 1 wave/SIMD, hence U = 1 there.)
+// No margin is left in two places: chain_stage_kernel<2> sits at exactly 256 VGPRs with no AGPRs,
+// so another compiler or a further edit can tip it to 1 wave/SIMD or into scratch, and the bf16
+// 8-row send (unchanged) is at 255 VGPRs + 2 AGPRs, 1 wave/SIMD. Check the remark after either.
 #include <algorithm>
 
 #include "chain.hpp"
@@ -31,6 +56,12 @@ namespace {
 
 bool misaligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) & 3; }
 bool misaligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) & 15; }
+
+// mxfp4 weight rows (w_e8m0 set): whole blocks of 32 columns, a lane's codes one aligned 8- or
+// 16-byte load, rows of codes and of scale bytes that hold K columns, and no fp8 row scales
+bool bad_mxfp4(const float* w_scale, int K, long ldw, long lde) {
+  return w_scale || K % 32 || ldw % 16 || ldw < K / 2 || lde < K / 32;
+}
 
 __device__ __forceinline__ bool reached(const uint32_t* flag, uint32_t target) {
   return (int)(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - target) >=
@@ -203,10 +234,79 @@ __device__ __forceinline__ void fp8_row_sum(const unsigned char* qr, const u16* 
   }
 }
 
+// ---- mxfp4 weight rows (w_e8m0 != nullptr) --------------------------------------------------
+// gemv_mxfp4.hip's sum, bit for bit. A lane's unit there is B columns of every chunk of 64 B:
+// B = 32 (a whole block) for a request of 1 or 2 rows when K >= C4_WHOLE_MIN_K, B = 16 (half a
+// block) otherwise, so lane l owns columns k0 + 64 B u + B l .. + B - 1, chunks ascending,
+// columns ascending, then wave_sum. The decoded code times its block scale times a bf16 x is
+// exact in fp32, so only this order fixes the result (not U, not how many neurons a wave holds)
+// -- but the order DOES depend on B, which is why both units exist here too. The decode is that
+// kernel's: the hardware conversion with the scale operand E << 23, a block with E == 0 has its
+// code word cleared first. There is no scale multiply after the reduction.
+constexpr int C4_WHOLE_MIN_K = 2048;  // gemv_mxfp4.hip's GEMV4_WHOLE_BLOCK_MIN_K
+template <int W>
+using qword_t = unsigned __attribute__((ext_vector_type(W)));  // W code words: 8 W columns
+
+// acc[m] += sum over the 8 columns of one code word of dec(code) * 2^(E - 127) * x[m][column],
+// columns ascending (byte c / 2 of the word, its low nibble first). `word` is already cleared
+// when E == 0.
+template <int M>
+__device__ __forceinline__ void fp4_fma8(unsigned word, float scale, const bf16x8_t (&xv)[M],
+                                         float (&acc)[M]) {
+  const f32x2_t d[4] = {__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, scale, 0),
+                        __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, scale, 1),
+                        __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, scale, 2),
+                        __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, scale, 3)};
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const float we = d[c >> 1][c & 1];
+#pragma unroll
+    for (int m = 0; m < M; ++m) acc[m] += we * bf2f((u16)xv[m][c]);
+  }
+}
+
+// One neuron's mxfp4 row (codes qr, scale bytes er) against `rows` <= M input rows in global
+// memory (chain_gemv_send; the loop of gemv_mxfp4_kernel: all loads of U chunks are issued
+// before any is used).
+template <int M, int U, int B>
+__device__ __forceinline__ void fp4_row_sum(const unsigned char* qr, const unsigned char* er,
+                                            const u16* x, long ldx, int rows, int K, int lane,
+                                            float (&acc)[M]) {
+  constexpr int CHUNK = 64 * B, W = B / 8;
+  for (int k0 = 0; k0 < K; k0 += CHUNK * U) {
+    qword_t<W> qv[U];
+    unsigned ev[U];
+    bf16x8_t xv[U][W][M];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = k0 + u * CHUNK + lane * B;
+      if (k < K) {  // K % 32 == 0: a lane's B columns are inside K or wholly outside
+        qv[u] = *(const qword_t<W>*)(qr + (k >> 1));
+        ev[u] = er[k >> 5];
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+          for (int j = 0; j < W; ++j)
+            xv[u][j][m] = m < rows ? *(const bf16x8_t*)(x + m * ldx + k + 8 * j) : bf16x8_t{};
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (k0 + u * CHUNK + lane * B < K) {
+        const float scale = __uint_as_float(ev[u] << 23);  // 2^(E - 127)
+#pragma unroll
+        for (int j = 0; j < W; ++j)  // word j holds columns k + 8 j .. k + 8 j + 7
+          fp4_fma8<M>(ev[u] ? qv[u][j] : 0u, scale, xv[u][j], acc);
+      }
+  }
+}
+
 // FP8: p.w holds e4m3 codes and p.w_scale their row scales; only the k loop and the scale
 // multiply differ -- the waits, hop_status, counter, header, flag and ack are the bf16 form's.
 // Registers: the file header; U as gemv_fp8.hip (8 rows at U = 4 cannot be held).
-template <int M, bool OUT_F32, bool FP8 = false>
+// B4 != 0: p.w holds packed e2m1 codes and p.w_e8m0 their block scales; B4 is the lane's unit
+// (16 or 32 columns, chosen by the launcher as gemv_mxfp4 chooses it), U as gemv_mxfp4.hip.
+template <int M, bool OUT_F32, bool FP8 = false, int B4 = 0>
 __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
   __shared__ uint32_t s_go;
   const unsigned t = threadIdx.x;
@@ -237,6 +337,10 @@ __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
     if constexpr (FP8) {
       fp8_row_sum<M, (M <= 2 ? 4 : 2)>((const unsigned char*)p.w + (long)n * p.ldw, p.x, p.ldx,
                                        p.rows, p.K, lane, acc);
+    } else if constexpr (B4 != 0) {
+      fp4_row_sum<M, (B4 == 32 || M > 2 ? 2 : 4), B4>(
+          (const unsigned char*)p.w + (long)n * p.ldw, p.w_e8m0 + (long)n * p.lde, p.x, p.ldx,
+          p.rows, p.K, lane, acc);
     } else {
       const uint16_t* wr = p.w + (long)n * p.ldw;
       constexpr int U = 4;
@@ -275,6 +379,9 @@ __global__ __launch_bounds__(256) void chain_gemv_send_kernel(ChainGemvSend p) {
         if (m == lane) v = acc[m];
       if constexpr (FP8) {  // gemv_fp8_kernel's epilogue, statement for statement
         v = __fmul_rn(p.w_scale[n], v);
+        v += p.bias ? p.bias[n] : 0.f;
+        v = act_fwd(v, p.act);
+      } else if constexpr (B4 != 0) {  // gemv_mxfp4_kernel's epilogue: no scale multiply
         v += p.bias ? p.bias[n] : 0.f;
         v = act_fwd(v, p.act);
       } else {
@@ -461,10 +568,91 @@ __device__ __forceinline__ void cs_layer_fp8(const ChainStage& p, const u16* xs,
   }
 }
 
-constexpr int CS_NB = 4;  // neurons per wave in flight (chain_stage_kernel, both weight forms)
+// cs_layer over mxfp4 weight rows (p.w_e8m0 != nullptr): per neuron fp4_row_sum's order for the
+// unit B, so the outputs are bitwise gemv_mxfp4.hip's at the same rows and K. A lane's B codes of
+// each of the NB neurons are one 8- or 16-byte global load and their block's scale one byte
+// load, all NB x U of them issued before any is used; its bf16 of a row are 16-byte LDS reads,
+// 8 columns (one code word) at a time as they are used, as cs_layer_fp8. A neuron past N gets
+// E = 0, which adds nothing, and is not written. The softmax `logits` get S + bias.
+// NB is CS_NB for every row capacity; NB, U, B and the registers: the file header.
+template <int M, int NB, int U, int B>
+__device__ __forceinline__ void cs_layer_mxfp4(const ChainStage& p, const u16* xs, int rows,
+                                               char* dst, float* logits) {
+  const unsigned t = threadIdx.x;
+  const int lane = t & 63;
+  constexpr int CHUNK = 64 * B, W = B / 8;
+  const unsigned char* q = (const unsigned char*)p.w;
+  for (int n0 = (blockIdx.x * CG_WAVES + (int)(t >> 6)) * NB; n0 < p.N;
+       n0 += gridDim.x * CG_WAVES * NB) {
+    float acc[NB][M];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[j][m] = 0.f;
+    for (int k0 = 0; k0 < p.K; k0 += CHUNK * U) {
+      qword_t<W> qv[NB][U];
+      unsigned ev[NB][U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + u * CHUNK + lane * B;
+        if (k < p.K) {  // K % 32 == 0: a lane's B columns are inside K or wholly outside
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            const bool in = n0 + j < p.N;
+            qv[j][u] = in ? *(const qword_t<W>*)(q + (long)(n0 + j) * p.ldw + (k >> 1))
+                          : qword_t<W>{};
+            ev[j][u] = in ? (unsigned)p.w_e8m0[(long)(n0 + j) * p.lde + (k >> 5)] : 0u;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + u * CHUNK + lane * B;
+        if (k < p.K) {
+#pragma unroll
+          for (int h = 0; h < W; ++h) {  // word h: columns k + 8 h .. k + 8 h + 7
+            bf16x8_t xv[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+              xv[m] = m < rows ? *(const bf16x8_t*)(xs + m * p.K + k + 8 * h) : bf16x8_t{};
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+              fp4_fma8<M>(ev[j][u] ? qv[j][u][h] : 0u, __uint_as_float(ev[j][u] << 23), xv,
+                          acc[j]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[j][m] = wave_sum(acc[j][m]);
+      const int n = n0 + j;
+      if (n < p.N && lane < rows) {
+        float v = 0.f;
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+          if (m == lane) v = acc[j][m];
+        v += p.bias ? p.bias[n] : 0.f;
+        if (logits) {
+          logits[lane * p.N + n] = v;
+        } else {
+          v = act_fwd(v, p.act);
+          if (p.out_f32)
+            ((float*)dst)[(long)lane * p.dst_ld + n] = v;
+          else
+            ((u16*)dst)[(long)lane * p.dst_ld + n] = f2bf(v);
+        }
+      }
+    }
+  }
+}
 
-// FP8: the layer reads e4m3 codes (cs_layer_fp8); everything else is shared.
-template <bool FP8>
+constexpr int CS_NB = 4;  // neurons per wave in flight (chain_stage_kernel, every weight form)
+
+// WT: the layer's weight form -- 0 bf16 (cs_layer), 1 e4m3 codes (cs_layer_fp8), 2 mxfp4
+// (cs_layer_mxfp4); everything else is shared.
+template <int WT>
 __global__ __launch_bounds__(256) void chain_stage_kernel(ChainStage p) {
   extern __shared__ __attribute__((aligned(16))) char cs_lds[];
   __shared__ uint32_t s_cmd[4];  // run, input status, rows, ack failure
@@ -600,13 +788,29 @@ __global__ __launch_bounds__(256) void chain_stage_kernel(ChainStage p) {
             __HIP_MEMORY_SCOPE_SYSTEM);
       }
       __syncthreads();
-      if constexpr (FP8) {
+      if constexpr (WT == 1) {
         switch (rows) {
           case 1: cs_layer_fp8<1, CS_NB, 4>(p, xs, rows, dst, logits); break;
           case 2: cs_layer_fp8<2, CS_NB, 4>(p, xs, rows, dst, logits); break;
           case 3:
           case 4: cs_layer_fp8<4, CS_NB, 2>(p, xs, rows, dst, logits); break;
           default: cs_layer_fp8<8, CS_NB, 2>(p, xs, rows, dst, logits); break;
+        }
+      } else if constexpr (WT == 2) {
+        const bool whole = p.K >= C4_WHOLE_MIN_K;  // 1 and 2 rows: gemv_mxfp4's unit rule
+        switch (rows) {
+          case 1:
+            if (whole) cs_layer_mxfp4<1, CS_NB, 2, 32>(p, xs, rows, dst, logits);
+            else cs_layer_mxfp4<1, CS_NB, 4, 16>(p, xs, rows, dst, logits);
+            break;
+          case 2:
+            if (whole) cs_layer_mxfp4<2, CS_NB, 2, 32>(p, xs, rows, dst, logits);
+            else cs_layer_mxfp4<2, CS_NB, 4, 16>(p, xs, rows, dst, logits);
+            break;
+          case 3:
+          case 4: cs_layer_mxfp4<4, CS_NB, 2, 16>(p, xs, rows, dst, logits); break;
+          // (U = 2 at 8 rows made the whole kernel 256 VGPRs + 12 AGPRs: 1 wave/SIMD)
+          default: cs_layer_mxfp4<8, CS_NB, 1, 16>(p, xs, rows, dst, logits); break;
         }
       } else {
         switch (rows) {
@@ -755,18 +959,43 @@ int chain_gemv_send(const ChainGemvSend& p, hipStream_t stream) {
   if (!p.next_flag || !p.dst_hdr || !p.err || !p.counter || !p.dst || !p.x || !p.w ||
       misaligned4(p.next_flag) || misaligned4(p.counter))
     return -1;
+  const bool fp4 = p.w_e8m0 != nullptr;  // (its ldw counts bytes of two codes each)
   if (p.rows < 1 || p.rows > GEMV_MAX_ROWS || p.N < 1 || p.K < 8 || p.K % 8 || p.ldx < p.K ||
-      p.ldw < p.K || p.ldx % 8 || p.ldw % 8 || p.dst_ld < p.N || misaligned16(p.x) ||
+      (!fp4 && p.ldw < p.K) || p.ldx % 8 || p.ldw % 8 || p.dst_ld < p.N || misaligned16(p.x) ||
       misaligned16(p.w))
     return -2;
   // fp8 rows: a lane's 16 codes are one aligned 16-byte load (ldw counts bytes)
   if (p.w_scale && (p.K % 16 || p.ldw % 16)) return -2;
+  if (fp4 && bad_mxfp4(p.w_scale, p.K, p.ldw, p.lde)) return -2;
   // the folded receive makes every workgroup wait on the input flag: at most CG_RECV_WG of
   // them, so a node's worth of waiting stages (a one-GPU rehearsal puts 8 on one GPU) stays
   // far below what the GPU holds at once
   constexpr int CG_RECV_WG = 64;
   const int wg = (p.N + CG_WAVES - 1) / CG_WAVES;
   const dim3 grid(p.in_flag ? std::min(wg, CG_RECV_WG) : wg), block(256);
+#define DNN_CG4(MM, BB)                                                                       \
+  if (p.out_f32)                                                                              \
+    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, true, false, BB>), grid, block, 0, stream, \
+                       p);                                                                    \
+  else                                                                                        \
+    hipLaunchKernelGGL((chain_gemv_send_kernel<MM, false, false, BB>), grid, block, 0,        \
+                       stream, p);
+  if (fp4) {  // the unit of gemv_mxfp4: a whole block for 1 and 2 rows from C4_WHOLE_MIN_K on
+    const bool whole = p.K >= C4_WHOLE_MIN_K;
+    switch (p.rows) {
+      case 1:
+        if (whole) { DNN_CG4(1, 32) } else { DNN_CG4(1, 16) }
+        break;
+      case 2:
+        if (whole) { DNN_CG4(2, 32) } else { DNN_CG4(2, 16) }
+        break;
+      case 3:
+      case 4: DNN_CG4(4, 16) break;
+      default: DNN_CG4(8, 16) break;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -9;
+  }
+#undef DNN_CG4
 #define DNN_CG(MM)                                                                            \
   if (p.w_scale && p.out_f32)                                                                 \
     hipLaunchKernelGGL((chain_gemv_send_kernel<MM, true, true>), grid, block, 0, stream, p);  \
@@ -799,12 +1028,16 @@ int chain_stage_run(const ChainStage& p, int workgroups, int share, hipStream_t 
       !p.next_flags || !p.ack || !p.stop || !p.done || !p.sync || misaligned4(p.in_flags) ||
       misaligned4(p.sync) || misaligned4(p.next_flags) || misaligned4(p.dst_hdr))
     return -1;
-  if (p.N < 1 || p.K < 8 || p.K % 8 || p.ldx < p.K || p.ldx % 8 || p.ldw < p.K || p.ldw % 8 ||
-      p.dst_ld < p.N || p.nslot < 2 || p.max_rows < 1 || p.max_rows > GEMV_MAX_ROWS ||
-      misaligned16(p.in_slots) || misaligned16(p.w) || p.epoch == 0)
+  const bool fp4 = p.w_e8m0 != nullptr;
+  if (p.N < 1 || p.K < 8 || p.K % 8 || p.ldx < p.K || p.ldx % 8 || (!fp4 && p.ldw < p.K) ||
+      p.ldw % 8 || p.dst_ld < p.N || p.nslot < 2 || p.max_rows < 1 ||
+      p.max_rows > GEMV_MAX_ROWS || misaligned16(p.in_slots) || misaligned16(p.w) || p.epoch == 0)
     return -2;
   if (p.w_scale && (p.K % 16 || p.ldw % 16)) return -2;  // fp8 rows, as chain_gemv_send
-  const auto kernel = p.w_scale ? chain_stage_kernel<true> : chain_stage_kernel<false>;
+  if (fp4 && bad_mxfp4(p.w_scale, p.K, p.ldw, p.lde)) return -2;
+  // (the occupancy below is taken from the kernel that is launched: each form has its own)
+  const auto kernel = fp4 ? chain_stage_kernel<2>
+                          : p.w_scale ? chain_stage_kernel<1> : chain_stage_kernel<0>;
   const long lds = (long)p.max_rows * p.K * 2 +
                    (p.act == ACT_SOFTMAX ? (long)p.max_rows * p.N * 4 : 0);
   if (lds > 64 * 1024) return -3;  // rows staged in LDS: K (and a softmax's N) bounded

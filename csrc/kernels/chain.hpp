@@ -107,6 +107,12 @@ struct ChainGemvSend {
   const float* w_scale;      // nullptr: bf16 weights. Else [N] fp32, one scale per output neuron
                              // (ops.quant_rows_fp8's format), and the rows are gemv_fp8.hip's bit
                              // for bit: act(fl32(w_scale[n] * S) + bias[n]), S in its lane order
+  const unsigned char* w_e8m0;  // nullptr: not mxfp4. Else (never with w_scale) w holds packed e2m1
+  long lde;                     // codes, [N][ldw] BYTES, two per byte, low nibble first, and this
+                                // [N][lde] e8m0 scale bytes, one per 32 columns
+                                // (ops.quant_rows_mxfp4's format; K % 32 == 0, ldw % 16 == 0,
+                                // ldw >= K / 2, lde >= K / 32). The rows are gemv_mxfp4.hip's bit
+                                // for bit: act(S + bias[n]), S in its lane order for rows and K
 };
 int chain_gemv_send(const ChainGemvSend& p, hipStream_t stream);
 
@@ -149,6 +155,9 @@ struct ChainStage {
   unsigned long long idle_ticks, timeout_ticks;
   const float* w_scale;      // nullptr: bf16 weights. Else [N] fp32 row scales of the e4m3 codes
                              // in w (K % 16 == 0, ldw % 16 == 0): gemv_fp8.hip's math, bitwise
+  const unsigned char* w_e8m0;  // nullptr: not mxfp4. Else (never with w_scale) w holds packed e2m1
+  long lde;                     // codes and this their e8m0 block scales, as ChainGemvSend's:
+                                // gemv_mxfp4.hip's math, bitwise, in the unit of the request's rows
 };
 // Returns the workgroups launched (>= 1; capped so that `share` persistent stages on this GPU
 // are all resident at once) or < 0 on a parameter / launch error.

@@ -65,6 +65,12 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "activations of every layer to e4m3 (one scale per row) and multiplies "
                          "the 4-bit codes by them on the block-scaled MFMA, the e8m0 block scales "
                          "as its scale operand, at any number of rows")
+    ap.add_argument("--mxfp4-chain", choices=["host", "device"], default="host",
+                    help="with --weights mxfp4 and --mode ranks, requests of <= 8 rows: host = "
+                         "the host chain, hop by hop; device = the device-side chain, whose "
+                         "kernels read the codes and block scales in place and answer bit for "
+                         "bit as the host chain's layer (ignored by bf16 and fp8 chains and by "
+                         "--mode local / workers, which have no device-side chain)")
     ap.add_argument("--port", type=int, default=5101)
     ap.add_argument("--layer-distribution", type=str, default=None,
                     help="override, e.g. '[1,1,1]'")
@@ -328,7 +334,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             json.dump({"stages": stage_entries, "port": a.port, "hop_timeout": a.hop_timeout,
                        "device": "cpu" if a.device == "cpu" else "auto",
                        "weights": a.weights, "fp8_gemm": a.fp8_gemm,
-                       "mxfp4_gemm": a.mxfp4_gemm}, open(plan_path, "w"))
+                       "mxfp4_gemm": a.mxfp4_gemm, "mxfp4_chain": a.mxfp4_chain},
+                      open(plan_path, "w"))
             job = spawn_ranks("docker_dist_nn_amd.serve.chain", ["--plan", plan_path], n_st,
                               devices=list(range(n_st)) if a.device != "cpu" else None,
                               names=[s["name"] for s in stage_entries])

@@ -101,7 +101,8 @@ class InferenceStage:
     the two sides of the 8/9-row line differ within the activation format's bound (2^-4
     relative per element plus half a subnormal step of the row); under ``"scratch"`` (the
     default) they do not. ``weight_operand`` still raises and an mxfp4 rank chain still serves on
-    the host chain.
+    the host chain by default; with ``--mxfp4-chain device`` the device-side chain reads the codes
+    and block scales in place through ``mxfp4_operand``.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
@@ -165,17 +166,29 @@ class InferenceStage:
         """Layer i's weight operand for a kernel that reads the stage's weights in place (the
         device-side chain): ``(tensor, row stride, (Np, Kp), scale)``. bf16: the padded weight,
         its stride in elements, ``None``. fp8: the e4m3 codes, their stride in bytes, the fp32
-        row scales. An mxfp4 stage has no such operand: the device-side chain's kernels do not
-        read that format."""
+        row scales. An mxfp4 stage has no operand of this shape (its scales are a matrix with a
+        stride of their own): ``mxfp4_operand`` gives it."""
         if self.weights == "mxfp4":
-            raise ValueError(f"({self.name}) weight_operand: the device-side chain does not "
-                             "read mxfp4 weights (codes plus block scales); an mxfp4 stage "
-                             "serves on the host chain")
+            raise ValueError(f"({self.name}) weight_operand: an mxfp4 stage holds codes plus "
+                             "block scales, which this tuple cannot carry; the device-side "
+                             "chain reads them through mxfp4_operand, and without "
+                             "--mxfp4-chain device an mxfp4 stage serves on the host chain")
         if self.weights == "fp8":
             q = self.q[i]
             return q, q.stride(0), tuple(q.shape), self.s[i]
         w = self.w[i]
         return w, w.stride(0), tuple(w.shape), None
+
+    def mxfp4_operand(self, i: int):
+        """Layer i's MXFP4 operand for a kernel that reads it in place (the device-side chain):
+        ``(codes, ldq, scales, lde, (Np, Kp))`` -- the stage's own resident tensors, the packed
+        e2m1 codes [Np][Kp / 2] and the e8m0 scale bytes [Np][Kp / 32], each with its row stride
+        in bytes. Raises for a bf16 or fp8 stage (``weight_operand`` is theirs)."""
+        if self.weights != "mxfp4":
+            raise ValueError(f"({self.name}) mxfp4_operand: the stage holds {self.weights} "
+                             "weights; weight_operand gives their operand")
+        q, e = self.q4[i], self.e4[i]
+        return q, q.stride(0), e, e.stride(0), (q.shape[0], 2 * q.shape[1])
 
     def resident_weight_bytes(self) -> int:
         """Bytes of the weight operands this stage keeps resident (biases, buffers and the bf16

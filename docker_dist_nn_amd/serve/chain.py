@@ -435,15 +435,26 @@ class ChainRank:
                            self.out_pad)
 
 
+# the plan's "mxfp4_chain": where an mxfp4 chain's requests of <= 8 rows go
+MXFP4_CHAINS = ("host", "device")
+
+
 def fast_chain_veto(plan: dict) -> Optional[str]:
     """Why a chain built from ``plan`` must not enable the device-side chain, or None. The
     device-side chain's kernels read bf16 and fp8 weight operands
-    (``InferenceStage.weight_operand``); an mxfp4 stage has neither, so such a chain serves
-    every request on the host chain."""
-    if plan.get("weights", "bf16") == "mxfp4":
-        return ("host chain: the device-side chain does not read mxfp4 weights "
-                "(DNN_CHAIN_FAST ignored)")
-    return None
+    (``InferenceStage.weight_operand``) and, opt-in, mxfp4 ones
+    (``InferenceStage.mxfp4_operand``): an mxfp4 chain serves every request on the host chain
+    unless the plan says ``"mxfp4_chain": "device"`` (``--mxfp4-chain``; ``"host"`` is the
+    default, any other value is an error). bf16 and fp8 chains ignore the entry."""
+    if plan.get("weights", "bf16") != "mxfp4":
+        return None
+    mode = plan.get("mxfp4_chain", "host")
+    if mode not in MXFP4_CHAINS:
+        raise ValueError(f"mxfp4_chain must be one of {MXFP4_CHAINS}, got {mode!r}")
+    if mode == "device":
+        return None
+    return ("host chain: the device-side chain reads mxfp4 weights only with "
+            "--mxfp4-chain device (DNN_CHAIN_FAST ignored)")
 
 
 def main(argv: Optional[list[str]] = None) -> int:

@@ -39,6 +39,17 @@ header read and a host send per hop. Here:
   scales in place (``InferenceStage.weight_operand``, the kernels' ``w_scale``) and sum in
   ``gemv_fp8``'s order, so a request's rows are bit for bit what ``ops.gemv_fp8`` -- the host
   chain's layer -- gives;
+* a stage serving from MXFP4 weights (``--weights mxfp4``) takes it when the plan says
+  ``"mxfp4_chain": "device"`` (``run_grpc_fcnn.py --mxfp4-chain device``; the default, ``host``,
+  keeps such a chain on the host chain, serve/chain.py ``fast_chain_veto``): the same three
+  kernels read the packed e2m1 codes and the e8m0 block scales in place
+  (``InferenceStage.mxfp4_operand``, the kernels' ``w_e8m0`` / ``lde``) and sum in
+  ``gemv_mxfp4``'s order for the request's rows and K -- a lane's unit there is a whole block for
+  1 and 2 rows at K >= 2048 and half a block otherwise, and the kernels follow it -- so a
+  request's rows are bit for bit what ``ops.gemv_mxfp4``, the host chain's layer, gives. The
+  earlier layers of a multi-layer stage go through ``InferenceStage.forward``, whose small-batch
+  layer is ``ops.gemv_mxfp4``; nothing here reads the stage's tensors but through the two
+  operand accessors. ``_persist_ok``'s LDS rule is the same: the rows are bf16;
 * larger requests and any set-up that cannot map its peers keep using the message-passing
   chain (serve/chain.py), which stays the fallback.
 """
@@ -425,6 +436,18 @@ class FastChain:
         return (self.dst + slot * self.max_rows * row_b, row_b,
                 self.next_flags + 4 * (F_HDR + 2 * slot), self.next_flags + 4 * (F_IN + slot))
 
+    def _weights(self, i: int) -> tuple[int, int, tuple[int, int], dict]:
+        """Layer i's weight operand as the chain kernels take it: (address of ``w``, its row
+        stride, (Np, Kp), the keyword arguments that name the format) -- ``w_scale`` for bf16
+        (0) and fp8 (the row scales), ``w_e8m0`` and ``lde`` for an mxfp4 stage, whose ``w`` is
+        the packed codes with a stride in bytes."""
+        st = self.cr.stage
+        if st.weights == "mxfp4":
+            q, ldq, e, lde, shape = st.mxfp4_operand(i)
+            return q.data_ptr(), ldq, shape, {"w_e8m0": e.data_ptr(), "lde": lde}
+        w, ldw, shape, scale = st.weight_operand(i)
+        return w.data_ptr(), ldw, shape, {"w_scale": 0 if scale is None else scale.data_ptr()}
+
     def _send(self, s: torch.cuda.Stream, out: Optional[torch.Tensor], rows: int, seq: int,
               status: int, in_hdr: int) -> None:
         slot = seq % NSLOT
@@ -449,7 +472,7 @@ class FastChain:
         L = len(st.layers)
         if L > 1:
             x = st.forward(rows, x=x, upto=L - 1)
-        w, ldw, (n_pad, _), scale = st.weight_operand(L - 1)
+        w, ldw, (n_pad, _), fmt = self._weights(L - 1)
         b = st.b[-1]
         slot = seq % NSLOT
         dst, dld, dhdr, dflag = self._dst(slot)
@@ -459,14 +482,14 @@ class FastChain:
             in_flag, prev_ack = _ptr(self.flags, F_IN + slot), self.prev_flags + 4 * F_ACK
         else:
             x_ptr, ldx, in_flag, prev_ack = x.data_ptr(), x.stride(0), 0, 0
-        self.n.chain_gemv_send(s.cuda_stream, x_ptr, ldx, w.data_ptr(), ldw,
+        self.n.chain_gemv_send(s.cuda_stream, x_ptr, ldx, w, ldw,
                                b.data_ptr(), ops.kernels._act(st.acts[-1]), rows, n_pad,
                                self.in_w if recv else x.shape[1], int(f32), dst,
                                dld // (4 if f32 else 2), dhdr, in_hdr, _ptr(self.flags, F_ERR),
                                self.rank, 0, self.ack_ptr,
                                (seq - NSLOT) & 0xFFFFFFFF, dflag, seq, prev_ack,
                                self.counter.data_ptr(), self.cr.hop_timeout, in_flag=in_flag,
-                               w_scale=0 if scale is None else scale.data_ptr())
+                               **fmt)
 
     # ---- rank 0 -------------------------------------------------------------------------------
     def predict(self, x: np.ndarray, timeout: Optional[float]) -> np.ndarray:
@@ -640,22 +663,21 @@ class FastChain:
         """Rank 0, one-layer stage, fused path: H2D + layer-and-send + result wait + D2H +
         ack + event as one native call (runtime/chain_host.cpp)."""
         st = self.cr.stage
-        w, ldw, (n_pad, _), scale = st.weight_operand(0)
+        w, ldw, (n_pad, _), fmt = self._weights(0)
         b = st.b[0]
         dst, dld, dhdr, dflag = self._dst(slot)
         base = self.res[slot]
         f32 = self.world == 1  # (rank 0 feeds rank 1's bf16 slot)
         self.host.request(
             slot, self.stream.cuda_stream, self.res_stream.cuda_stream, self.x0.data_ptr(),
-            self.h_in[slot].data_ptr(), rows * self.in_w * 2, w.data_ptr(), ldw,
+            self.h_in[slot].data_ptr(), rows * self.in_w * 2, w, ldw,
             b.data_ptr(), ops.kernels._act(st.acts[0]), rows, n_pad, self.in_w, dst,
             dld // (4 if f32 else 2), dhdr, _ptr(self.flags, F_ERR), _ptr(self.flags, F_ACK),
             (seq - NSLOT) & 0xFFFFFFFF, dflag, seq, self.counter.data_ptr(),
             self.cr.hop_timeout, _ptr(self.flags, F_RES + slot), _ptr(base, 2),
             base.data_ptr(), self.h_out[slot].data_ptr(),
             HDR + rows * self.res_w * 4, self.prev_flags_of_last() + 4 * F_ACK,
-            self.cr.hop_timeout * self.world,
-            w_scale=0 if scale is None else scale.data_ptr())
+            self.cr.hop_timeout * self.world, **fmt)
 
     def _result(self, seq: int, slot: int, rows: int, t_in: float) -> np.ndarray:
         """Decode the result slot's host copy (header, then fp32 rows) of request ``seq``."""
@@ -800,7 +822,7 @@ class FastChain:
             return False
         if self.cr.fault_stage == str(self.rank) or self.trace:
             return False  # fault injection and tracing act per request on the host
-        n_pad, k_pad = st.weight_operand(0)[2]
+        n_pad, k_pad = self._weights(0)[2]
         n = st.dims[-1] if st.acts[0] == "softmax" else n_pad
         lds = self.max_rows * self.in_w * 2 + (self.max_rows * n * 4
                                                 if st.acts[0] == "softmax" else 0)
@@ -808,7 +830,7 @@ class FastChain:
 
     def _persist_launch(self, start: int, epoch: int) -> None:
         st = self.cr.stage
-        w, ldw, (n_pad, _), scale = st.weight_operand(0)
+        w, ldw, (n_pad, _), fmt = self._weights(0)
         b, act = st.b[0], st.acts[0]
         last = self.rank == self.world - 1
         if last:  # rank 0's result slots: header, then fp32 rows
@@ -828,11 +850,11 @@ class FastChain:
         n_out = st.dims[-1] if act == "softmax" else n_pad
         self.workgroups = self.n.chain_stage_run(
             self.pstream.cuda_stream, in_flags, in_hdrs, in_slots, self.in_w, prev_ack,
-            w.data_ptr(), ldw, b.data_ptr(), ops.kernels._act(act), n_out, self.in_w,
+            w, ldw, b.data_ptr(), ops.kernels._act(act), n_out, self.in_w,
             int(last), dst, slot_b, self.out_w, hdr, hstride, nflags, self.ack_ptr, self._ctl_dev,
             self._ctl_dev + 4, self.sync.data_ptr(), start & 0xFFFFFFFF, epoch, self.rank, NSLOT,
             self.max_rows, PERSIST_IDLE_S, self.cr.hop_timeout, share=max(1, self.gpu_share),
-            w_scale=0 if scale is None else scale.data_ptr())
+            **fmt)
 
     def _persist_loop(self) -> None:
         """Keep the stage kernel running until the ring stops: relaunch it after an idle exit,
