@@ -1067,8 +1067,7 @@ PYBIND11_MODULE(_native, m) {
       .def(py::init<>())
       .def("begin_capture", [](dnn::GraphExec& g, uintptr_t s) { g.begin_capture(S(s)); })
       .def("end_capture", &dnn::GraphExec::end_capture)
-      .def("replay", [](dnn::GraphExec& g, uintptr_t s) { g.replay(S(s)); })
-      .def_property_readonly("captured", &dnn::GraphExec::captured)
+      .def("replay", [](dnn::GraphExec& g, uintptr_t s) { g.replay(S(s)); })      .def_property_readonly("captured", &dnn::GraphExec::captured)
       .def_property_readonly("num_nodes", &dnn::GraphExec::num_nodes)
       .def("reset", &dnn::GraphExec::reset);
   // ---- runtime: xGMI peer-to-peer pipeline transport (csrc/runtime/p2p.hpp) ---------------
@@ -1118,9 +1117,16 @@ PYBIND11_MODULE(_native, m) {
       [](uintptr_t p, size_t bytes) {
         // page-locks and maps existing host memory (e.g. a /dev/shm mapping shared by two
         // processes) for the GPU; returns its device pointer
-        if (hipHostRegister(reinterpret_cast<void*>(p), bytes, hipHostRegisterMapped) !=
-            hipSuccess)
-          throw std::runtime_error("hipHostRegister failed");
+        hipError_t e = hipHostRegister(reinterpret_cast<void*>(p), bytes, hipHostRegisterMapped);
+        if (e != hipSuccess) {
+          // Some platforms (a GPU passed through to a virtual machine, for one) cannot pin
+          // memory the process already has. The caller treats that as "facility missing" and
+          // goes on without it, so the error must not stay behind as the thread's last error:
+          // the next kernel launch's check would report it as its own.
+          (void)hipGetLastError();
+          throw std::runtime_error(std::string("hipHostRegister failed: ") +
+                                   hipGetErrorString(e));
+        }
         void* d = nullptr;
         if (hipHostGetDevicePointer(&d, reinterpret_cast<void*>(p), 0) != hipSuccess) {
           (void)hipHostUnregister(reinterpret_cast<void*>(p));

@@ -690,8 +690,12 @@ class FastChain:
         if self.trace:
             self._trace(seq, f"result hdr {hdr}")
         code, who = hdr[0] & 0xFF, (hdr[0] >> 8) & 0xFF
-        if hdr[2]:  # rank 0's own wait gave up: the last stage never answered
-            code, who = ST_DEADLINE, self.world - 1
+        if hdr[2]:
+            # rank 0's own wait gave up and no stage sent a status: the request is stuck at
+            # the first stage that has not processed it (a persistent stage kernel never sees
+            # a request that its producer did not send, so it cannot report the deadline)
+            code = ST_DEADLINE
+            who = self.cr.blame(seq) if self.cr.store is not None else self.world - 1
         if code != ST_OK:
             bad = self.cr.names[who % self.world]
             if code == ST_DEADLINE:
