@@ -28,6 +28,7 @@
 #include "kernels/linear_w8a8.hpp"
 #include "kernels/mlp_tail.hpp"
 #include "kernels/mxfp4.hpp"
+#include "kernels/stage_fwd.hpp"
 #include "runtime/blaslt.hpp"
 #include "runtime/chain_host.hpp"
 #include "runtime/graph.hpp"
@@ -66,6 +67,8 @@ static void check(int rc, const char* what) {
     if (std::string(what).rfind("gemm_bf16", 0) == 0) msg += dnn::gemm_error_string(rc);
     else if (std::string(what) == "mlp_tail")
       msg += dnn::mlp_tail_error(rc);
+    else if (std::string(what) == "stage_fwd")
+      msg += dnn::stage_fwd_error(rc);
     else if (std::string(what) == "blas_gemm") msg += dnn::blas_error(rc);
     else msg += "precondition/launch error code " + std::to_string(rc);
     if (rc == -9) msg += std::string(" (") + hipGetErrorString(hipGetLastError()) + ")";
@@ -410,6 +413,56 @@ PYBIND11_MODULE(_native, m) {
       py::arg("M"), py::arg("K3"), py::arg("N3"), py::arg("N4"), py::arg("n_cls"),
       py::arg("scale"), py::arg("act3"), py::arg("act2"), py::arg("stream"));
   m.def("mlp_tail_blocks", &dnn::mlp_tail_blocks);
+  // Fused stage forward. layers: (w, ldw, bias, N, K, act) per layer. Every pointer -- the
+  // input, each weight and bias, and the final output -- is routed through Program::fix, so a
+  // recorded launch stays valid under native replay.
+  m.def(
+      "stage_fwd",
+      [](uintptr_t x, long ldx, int M, int K0,
+         const std::vector<std::tuple<uintptr_t, long, uintptr_t, int, int, int>>& layers,
+         uintptr_t y, long ldy, int out_f32, int n_cls, int tile, uintptr_t stream) {
+        if (layers.size() > (size_t)dnn::STAGE_FWD_MAX_LAYERS)
+          check(-1, "stage_fwd");  // (more layers than StageFwdParams holds)
+        dnn::StageFwdParams p{};
+        p.x = P<const uint16_t>(x);
+        p.ldx = ldx;
+        p.M = M;
+        p.K0 = K0;
+        p.L = (int)layers.size();
+        for (int l = 0; l < p.L; ++l) {
+          dnn::StageFwdLayer& ly = p.layer[l];
+          ly.W = P<const uint16_t>(std::get<0>(layers[l]));
+          ly.ldw = std::get<1>(layers[l]);
+          ly.bias = P<const float>(std::get<2>(layers[l]));
+          ly.N = std::get<3>(layers[l]);
+          ly.K = std::get<4>(layers[l]);
+          ly.act = std::get<5>(layers[l]);
+        }
+        p.y = P<void>(y);
+        p.ldy = ldy;
+        p.out_f32 = out_f32;
+        p.n_cls = n_cls;
+        p.tile = tile;
+        launch(
+            "stage_fwd",
+            [=](hipStream_t s, const dnn::Program& R) {
+              dnn::StageFwdParams q = p;
+              q.x = R.fix(q.x);
+              q.y = R.fix(q.y);
+              for (int l = 0; l < q.L; ++l) {
+                q.layer[l].W = R.fix(q.layer[l].W);
+                q.layer[l].bias = R.fix(q.layer[l].bias);
+              }
+              return dnn::stage_fwd(q, s);
+            },
+            stream);
+      },
+      py::arg("x"), py::arg("ldx"), py::arg("M"), py::arg("K0"), py::arg("layers"), py::arg("y"),
+      py::arg("ldy"), py::arg("out_f32"), py::arg("n_cls"), py::arg("tile"), py::arg("stream"));
+  m.def("stage_fwd_limits", []() {
+    return std::make_tuple(dnn::STAGE_FWD_MAX_LAYERS, dnn::STAGE_FWD_MAX_WIDTH,
+                           dnn::STAGE_FWD_TILES);
+  });
   // Grouped GEMM launch (no epilogue extras: the split-K weight gradients of a step). problems:
   // (a, lda, b, ldb, c, ldc, c_split_stride, M, N, K, k_total, accumulate, splits)
   m.def(

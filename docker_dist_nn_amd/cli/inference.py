@@ -47,6 +47,12 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --local --weights fp8: how buckets of more than 8 rows run "
                          "(InferenceStage); w8a8 also quantises the activations to e4m3")
+    ap.add_argument("--stage-gemm", choices=["layers", "fused"], default="layers",
+                    help="with --local, bf16 weights, buckets of more than 8 rows: layers = one launch per "
+                         "layer; fused = all layers of a stage in one launch, the hidden "
+                         "activations kept in LDS (stages of 2..8 layers, padded widths after "
+                         "the input <= 512; anything else runs per layer). Same rounding of "
+                         "the hidden activations, another summation order: not bit for bit")
     ap.add_argument("--mxfp4-gemm", choices=["scratch", "w4a8"], default="scratch",
                     help="with --local --weights mxfp4: how buckets of more than 8 rows run "
                          "(InferenceStage); w4a8 quantises the activations to e4m3 and runs the "
@@ -92,7 +98,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             else torch.device("cuda", 0)
         eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
                               weights=a.weights, fp8_gemm=a.fp8_gemm,
-                              mxfp4_gemm=a.mxfp4_gemm)
+                              mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm)
 
         def call(batch):
             return eng.predict(batch)

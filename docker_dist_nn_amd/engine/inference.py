@@ -37,6 +37,7 @@ from .. import switches
 WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
 FP8_GEMMS = ("scratch", "direct", "w8a8")
 MXFP4_GEMMS = ("scratch", "w4a8")
+STAGE_GEMMS = ("layers", "fused")
 
 
 class InferenceStage:
@@ -103,18 +104,37 @@ class InferenceStage:
     default) they do not. ``weight_operand`` still raises and an mxfp4 rank chain still serves on
     the host chain by default; with ``--mxfp4-chain device`` the device-side chain reads the codes
     and block scales in place through ``mxfp4_operand``.
+
+    ``stage_gemm="fused"`` (bf16 weights; ignored by fp8 and mxfp4 stages) serves every bucket
+    of more than ``ops.GEMV_MAX_ROWS`` rows with ONE launch of ``ops.stage_fwd`` for all the
+    stage's layers instead of one launch per layer: the hidden activations stay in LDS and
+    ``buffers(rows)`` holds no hidden ``h`` buffers for such a bucket. It applies when
+    ``ops.stage_fwd_supported`` holds (2..8 layers, every padded width after the input at most
+    512, linear / relu / sigmoid layers, softmax on the last layer only) and ``upto`` is not
+    set; a last-layer softmax over more than 64 classes runs the fused kernel with a linear last
+    layer into fp32 and then ``ops.softmax_rows``. Everything else -- requests of <= 8 rows,
+    one-layer stages, a hidden softmax, a wider layer, ``upto`` -- runs the per-layer path
+    without a warning. ``"layers"`` (the default) is the per-layer path for every bucket. The
+    fused kernel rounds each hidden activation to bf16 exactly where the per-layer path does
+    but sums in its own order, so answers on the two sides of the 8/9-row line, and against
+    ``"layers"``, agree within fp32 summation error and one bf16 rounding of a hidden
+    activation, not bit for bit.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
                  expected_input: int, name: str = "layer", is_last: bool = True,
                  case_sensitive: bool = True, weights: str = "bf16",
-                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch"):
+                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
+                 stage_gemm: str = "layers"):
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
         if fp8_gemm not in FP8_GEMMS:
             raise ValueError(f"fp8_gemm must be one of {FP8_GEMMS}, got {fp8_gemm!r}")
         if mxfp4_gemm not in MXFP4_GEMMS:
             raise ValueError(f"mxfp4_gemm must be one of {MXFP4_GEMMS}, got {mxfp4_gemm!r}")
+        if stage_gemm not in STAGE_GEMMS:
+            raise ValueError(f"stage_gemm must be one of {STAGE_GEMMS}, got {stage_gemm!r}")
+        self.stage_gemm = stage_gemm
         self.weights = weights
         self.fp8_gemm = fp8_gemm
         self.mxfp4_gemm = mxfp4_gemm
@@ -150,6 +170,13 @@ class InferenceStage:
             else:
                 self.w.append(w)
             self.b.append(b.to(device))
+        # the fused kernel's activations: a last-layer softmax over more than one 64-wide tile
+        # runs linear into fp32 and ops.softmax_rows after it
+        self._fused_acts = list(self.acts)
+        if self.acts[-1] == "softmax" and self.dims[-1] > 64:
+            self._fused_acts[-1] = "linear"
+        self._fused_ok = (weights == "bf16" and stage_gemm == "fused" and
+                          ops.stage_fwd_supported(self.pads, self._fused_acts, self.dims[-1]))
         # fp8 / mxfp4, buckets > 8 rows: one bf16 layer
         self._wscratch: Optional[torch.Tensor] = None
         self._bufs: dict[int, dict] = {}
@@ -220,14 +247,37 @@ class InferenceStage:
                 for kp in self.pads[:-1]:
                     b["xq"].append(torch.zeros(rows, kp, dtype=torch.uint8, device=dev))
                     b["sx"].append(torch.zeros(rows, dtype=torch.float32, device=dev))
+            b["fused"] = self._fused(rows)
             for i, np_ in enumerate(self.pads[1:]):
                 last = i == len(self.layers) - 1
                 need_f32 = (last and self.is_last) or self.acts[i] == "softmax"
+                if b["fused"] and not last:  # hidden activations never leave the kernel
+                    b["h"].append(None)
+                    b["f32"].append(None)
+                    continue
                 b["h"].append(torch.zeros(rows, np_, dtype=torch.bfloat16, device=dev))
                 b["f32"].append(torch.zeros(rows, np_, dtype=torch.float32, device=dev)
                                 if need_f32 else None)
             self._bufs[rows] = b
         return b
+
+    def _fused(self, rows: int) -> bool:
+        """Whether a bucket of ``rows`` rows runs all its layers in one ops.stage_fwd."""
+        return self._fused_ok and rows > ops.GEMV_MAX_ROWS
+
+    def _forward_fused(self, b: dict, x: torch.Tensor) -> torch.Tensor:
+        n_out = self.dims[-1]
+        h, f = b["h"][-1], b["f32"][-1]
+        if self.acts[-1] != "softmax":
+            out = f if self.is_last else h
+            return ops.stage_fwd(x, self.w, self.b, self._fused_acts, out)
+        ops.stage_fwd(x, self.w, self.b, self._fused_acts, f, n_cls=n_out)
+        if self._fused_acts[-1] != "softmax":
+            ops.softmax_rows(f, f, n_out)
+        if self.is_last:
+            return f
+        ops.pack_bf16(f[:, :n_out], h)
+        return h
 
     def _w8a8(self, rows: int) -> bool:
         """Whether a bucket of ``rows`` rows runs on fp8 activations."""
@@ -284,6 +334,8 @@ class InferenceStage:
         b = self.buffers(rows)
         if x is None:
             x = b["x"]
+        if upto is None and b["fused"]:
+            return self._forward_fused(b, x)
         n = len(self.layers)
         for i in range(n if upto is None else upto):
             act = self.acts[i]
@@ -311,9 +363,11 @@ class InferenceEngine:
     def __init__(self, stage_layers: Sequence[Sequence[LayerWeights]], device: torch.device,
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
-                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch"):
+                 fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
+                 stage_gemm: str = "layers"):
         """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8",
-        ``mxfp4_gemm``: "scratch" or "w4a8" (see :class:`InferenceStage`), for every stage."""
+        ``mxfp4_gemm``: "scratch" or "w4a8", ``stage_gemm``: "layers" or "fused" (see
+        :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
@@ -321,7 +375,8 @@ class InferenceEngine:
         for i, ls in enumerate(stage_layers):
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
                                 is_last=i == len(stage_layers) - 1, weights=weights,
-                                fp8_gemm=fp8_gemm, mxfp4_gemm=mxfp4_gemm)
+                                fp8_gemm=fp8_gemm, mxfp4_gemm=mxfp4_gemm,
+                                stage_gemm=stage_gemm)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

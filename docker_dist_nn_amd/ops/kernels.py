@@ -688,6 +688,85 @@ def linear_fwd_w4a8(x, q, e, bias, y, act="relu", xq=None, sx=None, tile=0):
     return linear_w4a8(xq[:M, :K], sx, q, e, bias, y, act, tile)
 
 
+# csrc/kernels/stage_fwd.hpp (asserted on the GPU path)
+STAGE_FWD_MAX_LAYERS = 8
+STAGE_FWD_MAX_WIDTH = 512
+STAGE_FWD_TILES = 2
+
+
+def stage_fwd_supported(pads, acts, n_cls=0) -> bool:
+    """Whether the fused stage forward serves a stage: ``pads`` its padded widths (input first),
+    ``acts`` one activation name or code per layer, ``n_cls`` the real width of the last layer
+    (used when that layer is a softmax). 2 .. STAGE_FWD_MAX_LAYERS layers; every width a multiple
+    of 64, every output width <= STAGE_FWD_MAX_WIDTH; linear / relu / sigmoid per layer; softmax
+    on the last layer only, over one 64-wide tile with 1 <= n_cls <= 64."""
+    pads, acts = list(pads), [_act(a) for a in acts]
+    L = len(acts)
+    if len(pads) != L + 1 or not 2 <= L <= STAGE_FWD_MAX_LAYERS:
+        return False
+    if any(p < 64 or p % 64 for p in pads) or any(p > STAGE_FWD_MAX_WIDTH for p in pads[1:]):
+        return False
+    if any(a not in (0, 1, 2) for a in acts[:-1]) or acts[-1] not in (0, 1, 2, 3):
+        return False
+    if acts[-1] == 3 and not (pads[-1] == 64 and 1 <= n_cls <= 64):
+        return False
+    return True
+
+
+def stage_fwd(x, ws, biases, acts, y, n_cls=0, tile=0):
+    """All layers of a stage in ONE launch (csrc/kernels/stage_fwd.hip): h_0 = x, h_{l+1} =
+    bf16(act_l(h_l . ws[l]^T + biases[l])), the last layer into ``y`` (bf16 or fp32). Hidden
+    activations stay in LDS, rounded to bf16 once as the per-layer path rounds them; the sums
+    run in the kernel's own order, so the result is not bit for bit the per-layer chain's. x
+    bf16 [M][K0] with 16-byte aligned rows, ws[l] bf16 [N_l][N_{l-1}] padded weights read in
+    place (any row stride % 8), biases[l] fp32 [>= N_l] or None, y [>= M][>= N_last]; only rows
+    < M and columns < N_last of y are written. A softmax last layer (fp32 y) writes the
+    probabilities over the first ``n_cls`` columns and nothing beyond them. What the kernel
+    serves: :func:`stage_fwd_supported`. ``tile``: 0 = chosen by the launcher from M, 1 / 2
+    force 16 / 64 rows per workgroup (tests, benchmark). CPU tensors run the per-layer chain
+    (reference.stage_fwd)."""
+    acts = [_act(a) for a in acts]
+    L = len(ws)
+    if len(biases) != L or len(acts) != L:
+        raise ValueError("stage_fwd: one weight, bias and activation per layer")
+    _rows(x, "x", torch.bfloat16)
+    M, K = x.shape
+    pads = [K]
+    for l, (w, b) in enumerate(zip(ws, biases)):
+        _rows(w, f"ws[{l}]", torch.bfloat16)
+        if w.shape[1] != pads[-1]:
+            raise ValueError(f"stage_fwd: layer {l} takes {w.shape[1]} inputs, the layer before "
+                             f"gives {pads[-1]}")
+        if b is not None and (b.dtype != torch.float32 or b.numel() < w.shape[0] or
+                              not b.is_contiguous()):
+            raise ValueError("bias must be contiguous fp32 with >= N entries")
+        pads.append(w.shape[0])
+    if not stage_fwd_supported(pads, acts, n_cls):
+        raise ValueError(f"stage_fwd does not serve widths {pads} with activation codes {acts} "
+                         f"(n_cls {n_cls}): see stage_fwd_supported")
+    if M < 1 or y.dim() != 2 or y.shape[0] < M or y.shape[1] < pads[-1] or y.stride(1) != 1:
+        raise ValueError("stage_fwd operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if acts[-1] == 3 and y.dtype != torch.float32:
+        raise TypeError("a softmax last layer writes fp32 probabilities")
+    if not 0 <= int(tile) <= STAGE_FWD_TILES:
+        raise ValueError(f"stage_fwd tile must be 0..{STAGE_FWD_TILES}")
+    if not x.is_cuda:
+        return ref.stage_fwd(x, ws, biases, acts, y, n_cls)
+    assert native().stage_fwd_limits() == (STAGE_FWD_MAX_LAYERS, STAGE_FWD_MAX_WIDTH,
+                                           STAGE_FWD_TILES)
+    for name, t in (("x", x), *((f"ws[{l}]", w) for l, w in enumerate(ws))):
+        if t.data_ptr() % 16 or t.stride(0) % 8:
+            raise ValueError(f"stage_fwd: rows of {name} must be 16-byte aligned")
+    native().stage_fwd(_p(x), x.stride(0), M, K,
+                       [(_p(w), w.stride(0), _p(b), w.shape[0], w.shape[1], a)
+                        for w, b, a in zip(ws, biases, acts)],
+                       _p(y), y.stride(0), int(y.dtype == torch.float32), int(n_cls), int(tile),
+                       _stream(x))
+    return y
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

@@ -269,6 +269,27 @@ def softmax_rows(logits, out, n_cls, labels=None, pred=None, correct=None):
         correct += (am == labels[:rows].long()).sum().to(correct.dtype)
 
 
+def stage_fwd(x, ws, biases, acts, y, n_cls):
+    """The per-layer chain a serving stage runs: every layer is ``gemm`` (bf16 operands, fp32
+    sums, bias, activation), a hidden activation is rounded to bf16 once, the last layer goes
+    into ``y`` in y's type; a softmax last layer is its fp32 logits then ``softmax_rows`` over
+    the first n_cls columns, written for those columns only. acts: Act codes."""
+    M = x.shape[0]
+    h = x
+    for l, (w, b, act) in enumerate(zip(ws, biases, acts)):
+        N, K = w.shape
+        last = l == len(ws) - 1
+        if last and act == 3:
+            z = torch.zeros(M, N, dtype=torch.float32)
+            gemm(h, w, z, layout_a=0, layout_b=0, M=M, N=N, K=K, bias=b, act=0)
+            softmax_rows(z, y, n_cls)
+            return y
+        out = y if last else torch.zeros(M, N, dtype=torch.bfloat16)
+        gemm(h, w, out, layout_a=0, layout_b=0, M=M, N=N, K=K, bias=b, act=act)
+        h = out
+    return y
+
+
 def colsum_partial(x, part, n_part):
     rows, cols = x.shape
     per = (rows + n_part - 1) // n_part

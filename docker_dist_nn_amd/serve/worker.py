@@ -15,8 +15,9 @@ weight format of the stage's engine (run_grpc_fcnn.py --weights), and STAGE_FP8_
 "direct" or "w8a8", how an fp8 stage runs buckets of more than 8 rows (--fp8-gemm; "w8a8" also
 quantises each layer's activations to e4m3; ignored by an mxfp4 stage), and STAGE_MXFP4_GEMM,
 "scratch" (default) or "w4a8", how an mxfp4 stage runs those buckets (--mxfp4-gemm; "w4a8" runs
-the 4-bit codes against e4m3 activations; ignored by bf16 and fp8 stages). The values are passed
-to the engine unchanged.
+the 4-bit codes against e4m3 activations; ignored by bf16 and fp8 stages), and STAGE_GEMM,
+"layers" (default) or "fused", whether a bf16 stage runs those buckets one launch per layer or
+all its layers in one (--stage-gemm). The values are passed to the engine unchanged.
 
 This worker keeps that contract, the LayerService protocol and the error mapping of
 grpc_node.py:99-158 (ValueError -> INVALID_ARGUMENT, a failed forward keeps the downstream
@@ -82,7 +83,8 @@ class StageWorker:
                                names=[self.container_name],
                                weights=env.get("STAGE_WEIGHTS", "bf16") or "bf16",
                                fp8_gemm=env.get("STAGE_FP8_GEMM", "scratch") or "scratch",
-                               mxfp4_gemm=env.get("STAGE_MXFP4_GEMM", "scratch") or "scratch")
+                               mxfp4_gemm=env.get("STAGE_MXFP4_GEMM", "scratch") or "scratch",
+                               stage_gemm=env.get("STAGE_GEMM", "layers") or "layers")
 
     def _client(self):
         from .ingress import LayerClient
