@@ -24,6 +24,7 @@
 #include "kernels/gemv_fp8.hpp"
 #include "kernels/gemv_mxfp4.hpp"
 #include "kernels/linear_fp8.hpp"
+#include "kernels/linear_stream.hpp"
 #include "kernels/linear_w4a8.hpp"
 #include "kernels/linear_w8a8.hpp"
 #include "kernels/mlp_tail.hpp"
@@ -241,6 +242,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("ldq"), py::arg("scale"),
       py::arg("bias"), py::arg("y"), py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("act"), py::arg("out_f32"), py::arg("stream"), py::arg("tile") = 0);
+  m.def(
+      "linear_stream",
+      [](uintptr_t x, long ldx, uintptr_t w, long ldw, uintptr_t bias, uintptr_t y, long ldy,
+         int M, int N, int K, int act, int out_f32, uintptr_t stream, int tile) {
+        launch(
+            "linear_stream",
+            [=](hipStream_t s, const dnn::Program& R) {
+              return dnn::linear_stream(R.fix(P<const uint16_t>(x)), ldx,
+                                        R.fix(P<const uint16_t>(w)), ldw,
+                                        R.fix(P<const float>(bias)), R.fix(P<void>(y)), ldy, M, N,
+                                        K, act, out_f32, tile, s);
+            },
+            stream);
+      },
+      py::arg("x"), py::arg("ldx"), py::arg("w"), py::arg("ldw"), py::arg("bias"), py::arg("y"),
+      py::arg("ldy"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"),
+      py::arg("out_f32"), py::arg("stream"), py::arg("tile") = 0);
+  m.def("linear_stream_tiles", []() { return dnn::LINEAR_STREAM_TILES; });
   m.def(
       "linear_w8a8",
       [](uintptr_t xq, long ldxq, uintptr_t sx, uintptr_t q, long ldq, uintptr_t sw,

@@ -59,6 +59,11 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "GEMM on the codes, up to ops.FP8_DIRECT_MAX_ROWS rows; w8a8 = also "
                          "quantises the activations of every layer to e4m3 (one scale per row) "
                          "and multiplies codes by codes on the fp8 MFMA, at any number of rows")
+    ap.add_argument("--bf16-gemm", choices=["tiled", "stream"], default="tiled",
+                    help="bf16 weights, buckets of 9 .. ops.BF16_STREAM_MAX_ROWS rows: tiled = "
+                         "the training GEMM (ops.linear_fwd); stream = the weight-streaming "
+                         "GEMM (ops.linear_fwd_stream: weights straight into the MFMA "
+                         "registers, K split inside the workgroup)")
     ap.add_argument("--stage-gemm", choices=["layers", "fused"], default="layers",
                     help="bf16 stages, buckets of more than 8 rows: layers = one launch per "
                          "layer; fused = all layers of a stage in one launch, the hidden "
@@ -299,7 +304,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             eng = InferenceEngine([mc.layers[p.layer_start:p.layer_end] for p in plans], dev,
                                   expected_input=input_dim, names=[s["name"] for s in stage_entries],
                                   weights=a.weights, fp8_gemm=a.fp8_gemm,
-                                  mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm)
+                                  mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm,
+                                  bf16_gemm=a.bf16_gemm)
             server = serve(eng.predict, port=a.port, name=stage_entries[0]["name"])
         elif mode == "workers":
             from ..launch import spawn_workers, wait_for_port
@@ -325,6 +331,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                 e["STAGE_FP8_GEMM"] = a.fp8_gemm
                 e["STAGE_MXFP4_GEMM"] = a.mxfp4_gemm
                 e["STAGE_GEMM"] = a.stage_gemm
+                e["STAGE_BF16_GEMM"] = a.bf16_gemm
                 e["LOCAL_RANK"] = str(k)
                 stage_envs.append(e)
             job = spawn_workers("docker_dist_nn_amd.serve.worker", stage_envs,
@@ -342,7 +349,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                        "device": "cpu" if a.device == "cpu" else "auto",
                        "weights": a.weights, "fp8_gemm": a.fp8_gemm,
                        "mxfp4_gemm": a.mxfp4_gemm, "mxfp4_chain": a.mxfp4_chain,
-                       "stage_gemm": a.stage_gemm},
+                       "stage_gemm": a.stage_gemm, "bf16_gemm": a.bf16_gemm},
                       open(plan_path, "w"))
             job = spawn_ranks("docker_dist_nn_amd.serve.chain", ["--plan", plan_path], n_st,
                               devices=list(range(n_st)) if a.device != "cpu" else None,

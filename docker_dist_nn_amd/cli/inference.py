@@ -47,6 +47,11 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
     ap.add_argument("--fp8-gemm", choices=["scratch", "direct", "w8a8"], default="scratch",
                     help="with --local --weights fp8: how buckets of more than 8 rows run "
                          "(InferenceStage); w8a8 also quantises the activations to e4m3")
+    ap.add_argument("--bf16-gemm", choices=["tiled", "stream"], default="tiled",
+                    help="with --local, bf16 weights, buckets of 9 .. "
+                         "ops.BF16_STREAM_MAX_ROWS rows: tiled = the training GEMM (ops.linear_fwd); stream = the weight-streaming "
+                         "GEMM (ops.linear_fwd_stream: weights straight into the MFMA "
+                         "registers, K split inside the workgroup)")
     ap.add_argument("--stage-gemm", choices=["layers", "fused"], default="layers",
                     help="with --local, bf16 weights, buckets of more than 8 rows: layers = one launch per "
                          "layer; fused = all layers of a stage in one launch, the hidden "
@@ -98,7 +103,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             else torch.device("cuda", 0)
         eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
                               weights=a.weights, fp8_gemm=a.fp8_gemm,
-                              mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm)
+                              mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm,
+                              bf16_gemm=a.bf16_gemm)
 
         def call(batch):
             return eng.predict(batch)

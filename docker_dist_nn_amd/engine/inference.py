@@ -38,6 +38,7 @@ WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
 FP8_GEMMS = ("scratch", "direct", "w8a8")
 MXFP4_GEMMS = ("scratch", "w4a8")
 STAGE_GEMMS = ("layers", "fused")
+BF16_GEMMS = ("tiled", "stream")
 
 
 class InferenceStage:
@@ -119,13 +120,23 @@ class InferenceStage:
     but sums in its own order, so answers on the two sides of the 8/9-row line, and against
     ``"layers"``, agree within fp32 summation error and one bf16 rounding of a hidden
     activation, not bit for bit.
+
+    ``bf16_gemm="stream"`` (bf16 weights; ignored by fp8 and mxfp4 stages) runs every layer of
+    a bucket of 9 .. ``ops.BF16_STREAM_MAX_ROWS`` rows on ``ops.linear_fwd_stream``, the
+    weight-streaming GEMM (weights straight into the MFMA operand registers, K split inside the
+    workgroup in a fixed order), instead of the training GEMM of ``ops.linear_fwd``; a softmax
+    layer runs linear into fp32 and then ``ops.softmax_rows``, as on the default path. Requests
+    of <= 8 rows keep ``ops.gemv`` and larger buckets ``ops.linear_fwd``; where
+    ``stage_gemm="fused"`` applies it takes the bucket first. No buffer is added. The sums are
+    taken in the kernel's own order, so answers agree with ``"tiled"`` (the default: today's
+    path, bit for bit) within fp32 summation error, not bit for bit.
     """
 
     def __init__(self, layers: Sequence[LayerWeights], device: torch.device, *,
                  expected_input: int, name: str = "layer", is_last: bool = True,
                  case_sensitive: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
-                 stage_gemm: str = "layers"):
+                 stage_gemm: str = "layers", bf16_gemm: str = "tiled"):
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
         if fp8_gemm not in FP8_GEMMS:
@@ -134,7 +145,10 @@ class InferenceStage:
             raise ValueError(f"mxfp4_gemm must be one of {MXFP4_GEMMS}, got {mxfp4_gemm!r}")
         if stage_gemm not in STAGE_GEMMS:
             raise ValueError(f"stage_gemm must be one of {STAGE_GEMMS}, got {stage_gemm!r}")
+        if bf16_gemm not in BF16_GEMMS:
+            raise ValueError(f"bf16_gemm must be one of {BF16_GEMMS}, got {bf16_gemm!r}")
         self.stage_gemm = stage_gemm
+        self.bf16_gemm = bf16_gemm
         self.weights = weights
         self.fp8_gemm = fp8_gemm
         self.mxfp4_gemm = mxfp4_gemm
@@ -292,7 +306,11 @@ class InferenceStage:
     def _linear(self, i: int, x: torch.Tensor, y: torch.Tensor, act: str) -> None:
         """y = act(x . W_i^T + b_i) from the stage's weight format."""
         if self.weights == "bf16":
-            ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
+            if (self.bf16_gemm == "stream"
+                    and ops.GEMV_MAX_ROWS < x.shape[0] <= ops.BF16_STREAM_MAX_ROWS):
+                ops.linear_fwd_stream(x, self.w[i], self.b[i], y, act=act)
+            else:
+                ops.linear_fwd(x, self.w[i], self.b[i], y, act=act)
         elif self.weights == "mxfp4":
             if x.shape[0] <= ops.GEMV_MAX_ROWS:
                 ops.gemv_mxfp4(x, self.q4[i], self.e4[i], self.b[i], y, act=act)
@@ -364,10 +382,10 @@ class InferenceEngine:
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
-                 stage_gemm: str = "layers"):
+                 stage_gemm: str = "layers", bf16_gemm: str = "tiled"):
         """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8",
-        ``mxfp4_gemm``: "scratch" or "w4a8", ``stage_gemm``: "layers" or "fused" (see
-        :class:`InferenceStage`), for every stage."""
+        ``mxfp4_gemm``: "scratch" or "w4a8", ``stage_gemm``: "layers" or "fused", ``bf16_gemm``:
+        "tiled" or "stream" (see :class:`InferenceStage`), for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
@@ -376,7 +394,7 @@ class InferenceEngine:
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
                                 is_last=i == len(stage_layers) - 1, weights=weights,
                                 fp8_gemm=fp8_gemm, mxfp4_gemm=mxfp4_gemm,
-                                stage_gemm=stage_gemm)
+                                stage_gemm=stage_gemm, bf16_gemm=bf16_gemm)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

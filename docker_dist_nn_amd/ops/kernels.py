@@ -578,6 +578,55 @@ def linear_fwd_fp8(x, q, scale, bias, y, act="relu", tile=0):
     return y
 
 
+LINEAR_STREAM_TILES = 6  # csrc/kernels/linear_stream.hpp (asserted on the GPU path)
+
+# Largest row bucket the serving engine runs on linear_fwd_stream under bf16_gemm="stream";
+# larger buckets keep linear_fwd. Measured (bench/linear_stream_bench.py,
+# profiles/linear_stream/linear_stream_bench.jsonl, 8192 x 8192 read cold, stream against
+# linear_fwd): the largest power-of-two bucket at which stream does not lose. 512 rows: 100.5
+# against 112.2 us (wins; spreads <= 3.6 %); 1024 rows: 187.0 against 153.3 us (loses).
+BF16_STREAM_MAX_ROWS = 512
+
+
+def linear_fwd_stream(x, w, bias, y, act="relu", tile=0):
+    """linear_fwd's definition, y[m][n] = act(sum_k x[m][k] * w[n][k] + bias[n]), on the
+    weight-streaming GEMM (csrc/kernels/linear_stream.hip): the weights go from global memory
+    straight into the MFMA's operand registers, only the x tile is shared through LDS, and K is
+    split 2- or 4-way inside the workgroup with a fixed summation order. Made for serving
+    buckets of 9 .. BF16_STREAM_MAX_ROWS rows of a wide layer, which are bound by the bytes of
+    w; any M >= 1 is served. Up to GEMV_MAX_ROWS rows with ``tile == 0`` run ops.gemv.
+    x bf16 [M][K], w bf16 [N][>=K], rows of both 16-byte aligned, bias fp32 [>=N] or None, y
+    bf16 or fp32 [>=M][>=N] with any row stride; K % 32 == 0.
+    ``tile``: 0 = chosen by the launcher, 1 .. LINEAR_STREAM_TILES force one (linear_stream.hpp;
+    tests, benchmark)."""
+    M, K = x.shape
+    N = w.shape[0]
+    if K % 32:
+        raise ValueError("linear_fwd_stream takes K % 32 == 0")
+    _rows(x, "x", torch.bfloat16)
+    _rows(w, "w", torch.bfloat16)
+    if w.shape[1] < K or y.shape[0] < M or y.shape[1] < N or y.stride(1) != 1:
+        raise ValueError("linear_fwd_stream operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < N):
+        raise ValueError("bias must be fp32 with >= N entries")
+    if not 0 <= int(tile) <= LINEAR_STREAM_TILES:
+        raise ValueError(f"linear_fwd_stream tile must be 0..{LINEAR_STREAM_TILES}")
+    if not x.is_cuda:
+        return gemm(x, w, y, layout_a=KMAJ, layout_b=KMAJ, M=M, N=N, K=K, bias=bias, act=act)
+    for name, t in (("x", x), ("w", w)):
+        if t.data_ptr() % 16 or t.stride(0) % 8:
+            raise ValueError(f"linear_fwd_stream: rows of {name} must be 16-byte aligned")
+    if M <= GEMV_MAX_ROWS and not tile:
+        return gemv(x, w, bias, y, act)
+    assert native().linear_stream_tiles() == LINEAR_STREAM_TILES
+    native().linear_stream(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(y), y.stride(0),
+                           M, N, K, _act(act), int(y.dtype == torch.float32), _stream(x),
+                           int(tile))
+    return y
+
+
 def linear_w8a8(xq, sx, q, scale, bias, y, act="relu", tile=0):
     """Forward layer with e4m3 codes on both operands, each in the format of quant_rows_fp8:
     y[m][n] = act(fl32(sx[m] * fl32(scale[n] * sum_k e4m3(xq[m][k]) * e4m3(q[n][k]))) + bias[n])

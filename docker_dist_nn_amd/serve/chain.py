@@ -491,7 +491,8 @@ def main(argv: Optional[list[str]] = None) -> int:
                            is_last=rank == world - 1, weights=plan.get("weights", "bf16"),
                            fp8_gemm=plan.get("fp8_gemm", "scratch"),
                            mxfp4_gemm=plan.get("mxfp4_gemm", "scratch"),
-                           stage_gemm=plan.get("stage_gemm", "layers"))
+                           stage_gemm=plan.get("stage_gemm", "layers"),
+                           bf16_gemm=plan.get("bf16_gemm", "tiled"))
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))
     if world > 1 and use_gpu and switches.get("DNN_CHAIN_FAST") == "1":
