@@ -30,6 +30,7 @@
 #include "kernels/mlp_tail.hpp"
 #include "kernels/mxfp4.hpp"
 #include "kernels/stage_fwd.hpp"
+#include "kernels/xent_stream.hpp"
 #include "runtime/blaslt.hpp"
 #include "runtime/chain_host.hpp"
 #include "runtime/graph.hpp"
@@ -353,6 +354,28 @@ PYBIND11_MODULE(_native, m) {
         py::arg("loss_part"), py::arg("correct"), py::arg("stream"), py::arg("colsum") = 0,
         py::arg("ld_colsum") = 0);
   m.def("softmax_xent_blocks", &dnn::softmax_xent_blocks);
+  m.def("xent_stream",
+        [](uintptr_t x, long ldx, uintptr_t w, long ldw, uintptr_t bias, uintptr_t labels,
+           uintptr_t dz, long ld_dz, int M, int N, int K, int n_cls, float scale,
+           uintptr_t loss_part, uintptr_t correct, uintptr_t colsum, long ld_colsum,
+           uintptr_t stream) {
+          launch(
+              "xent_stream",
+              [=](hipStream_t s, const dnn::Program& R) {
+                return dnn::xent_stream(R.fix(P<const uint16_t>(x)), ldx,
+                                        R.fix(P<const uint16_t>(w)), ldw,
+                                        R.fix(P<const float>(bias)), R.fix(P<const int>(labels)),
+                                        R.fix(P<uint16_t>(dz)), ld_dz, M, N, K, n_cls, scale,
+                                        R.fix(P<float>(loss_part)), R.fix(P<int>(correct)),
+                                        R.fix(P<float>(colsum)), ld_colsum, s);
+              },
+              stream);
+        },
+        py::arg("x"), py::arg("ldx"), py::arg("w"), py::arg("ldw"), py::arg("bias"),
+        py::arg("labels"), py::arg("dz"), py::arg("ld_dz"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("n_cls"), py::arg("scale"), py::arg("loss_part"),
+        py::arg("correct"), py::arg("colsum"), py::arg("ld_colsum"), py::arg("stream"));
+  m.def("xent_stream_max_k", []() { return dnn::XENT_STREAM_MAX_K; });
   m.def("dense_loss",
         [](uintptr_t z, long ld_z, uintptr_t t, long ld_t, uintptr_t row_ok, uintptr_t dz,
            long ld_dz, int rows, int n_out, int width, int loss, int act, float scale,

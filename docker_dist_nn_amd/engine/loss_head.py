@@ -13,6 +13,10 @@ TailHead       GEMM-fused CE possible, GPU, >= 3 local     ops.mlp_tail: forward
                takes, DNN_TAIL=1
 FusedXentHead  softmax_ce, 64 or 128 padded classes,       ops.linear_fwd_xent (logits never
                DNN_FUSED_XENT=1                            exist in memory)
+StreamXentHead softmax_ce the GEMM-fused head does not      ops.linear_xent_stream (any class
+               take, ops.xent_stream_supported (last       count; logits never exist in memory)
+               layer's padded input <= 1024 wide),
+               DNN_XENT_STREAM=1 (default 0)
 XentHead       any other softmax_ce                        ops.linear_fwd to fp32 logits +
                                                            ops.softmax_xent
 DenseHead      loss mse | bce                              ops.linear_fwd to fp32
@@ -109,7 +113,10 @@ class LossHead:
             return DenseHead(st)
         # the last layer's softmax-CE is fused into its GEMM epilogue when the padded class
         # count is one 64/128-wide tile
-        if not (st.geoms[-1].np_ in (64, 128) and switches.get("DNN_FUSED_XENT") == "1"):
+        gl = st.geoms[-1]
+        if not (gl.np_ in (64, 128) and switches.get("DNN_FUSED_XENT") == "1"):
+            if switches.get("DNN_XENT_STREAM") == "1" and ops.xent_stream_supported(gl.kp, gl.np_):
+                return StreamXentHead(st)
             return XentHead(st)
         return TailHead(st) if TailHead.supported(st) else FusedXentHead(st)
 
@@ -169,6 +176,23 @@ class XentHead(LossHead):
         ops.linear_fwd(st.input_of(i)[r], p.wbf(i), p.b32(i), y, act="linear")  # fp32 logits
         ops.softmax_xent(y, self.labels.cur[r], st.dz[i][r], st.n_cls, 1.0 / st.global_batch,
                          lp, cr, colsum=st._bpart(i, j))
+
+
+class StreamXentHead(LossHead):
+    """Last layer + softmax cross-entropy of any class count in one kernel that sweeps the class
+    tiles twice (csrc/kernels/xent_stream.hip): no logits matrix, XentHead's partials."""
+
+    logits = False
+
+    def __init__(self, st):
+        super().__init__(st, ops.xent_blocks(st.mb))
+
+    def forward(self, st, j: int) -> None:
+        i, r, p = len(st.geoms) - 1, st.rows_of(j), st.params
+        lp, cr = self._parts(j)
+        ops.linear_xent_stream(st.input_of(i)[r], p.wbf(i), p.b32(i), st.dz[i][r],
+                               self.labels.cur[r], st.n_cls, 1.0 / st.global_batch, lp, cr,
+                               colsum=st._bpart(i, j))
 
 
 class FusedXentHead(LossHead):

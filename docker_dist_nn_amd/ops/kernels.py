@@ -1009,6 +1009,68 @@ def softmax_xent(logits, labels, dz, n_cls, scale, loss_part=None, correct=None,
                           colsum.stride(0) if colsum is not None else 0)
 
 
+XENT_STREAM_MAX_K = 1024  # csrc/kernels/xent_stream.hpp (asserted on the GPU path)
+
+
+def xent_stream_supported(kp: int, np_: int) -> bool:
+    """Can linear_xent_stream serve a last layer of padded geometry [np_][kp]? (rows: % 64)"""
+    return kp % 64 == 0 and 64 <= kp <= XENT_STREAM_MAX_K and np_ % 64 == 0 and np_ >= 64
+
+
+def linear_xent_stream(x, w, bias, dz, labels, n_cls, scale, loss_part=None, correct=None,
+                       colsum=None):
+    """linear_fwd_xent's contract for ANY class count, with softmax_xent's 64-row partials, and
+    no logits matrix (csrc/kernels/xent_stream.hip): dz[M][Np] = (softmax(x.w^T + b) - onehot) *
+    scale over the first n_cls columns (zeros in the others and in rows with a label < 0),
+    loss_part / correct / colsum[xent_blocks(M)][>=Np] per 64-row block, written. A workgroup
+    keeps its 64 rows of x in LDS and sweeps the class tiles twice, the weights streamed from
+    memory into the MFMA's operand registers.
+    x bf16 [M][Kp], w bf16 [Np][>=Kp], rows of both 16-byte aligned, bias fp32 [>=Np], dz bf16
+    [M][Np] with any row stride, labels int32 [>=M]; M % 64 == 0 and xent_stream_supported(Kp,
+    Np). Rows n_cls..Np of w and bias may hold anything."""
+    M, K = x.shape
+    N = w.shape[0]
+    nb = xent_blocks(M)
+    if M % XENT_ROWS_PER_BLOCK:
+        raise ValueError(f"linear_xent_stream takes rows % {XENT_ROWS_PER_BLOCK} == 0, got {M}")
+    if K > XENT_STREAM_MAX_K:
+        raise ValueError(f"linear_xent_stream takes Kp <= {XENT_STREAM_MAX_K}, got {K}")
+    if not xent_stream_supported(K, N) or not 0 < n_cls <= N:
+        raise ValueError("linear_xent_stream takes Kp % 64 == 0, Np % 64 == 0, 0 < n_cls <= Np")
+    _rows(x, "x", torch.bfloat16)
+    _rows(w, "w", torch.bfloat16)
+    _rows(dz, "dz", torch.bfloat16)
+    if w.shape[1] < K or dz.shape[0] < M or dz.shape[1] < N:
+        raise ValueError("linear_xent_stream operand shapes do not match")
+    if bias is None or bias.dtype != torch.float32 or bias.numel() < N:
+        raise ValueError("linear_xent_stream needs an fp32 bias with >= Np entries")
+    if labels.dtype != torch.int32 or labels.numel() < M:
+        raise ValueError("labels must be int32 with one entry per row")
+    if loss_part is not None and (loss_part.dtype != torch.float32 or loss_part.numel() < nb):
+        raise ValueError(f"loss_part needs {nb} fp32 entries")
+    if correct is not None and (correct.dtype != torch.int32 or correct.numel() < nb):
+        raise ValueError(f"correct needs {nb} int32 entries")
+    if colsum is not None and (colsum.dtype != torch.float32 or colsum.dim() != 2 or
+                               colsum.shape[0] < nb or colsum.shape[1] < N or
+                               colsum.stride(1) != 1):
+        raise ValueError(f"colsum must be fp32 [{nb}][>={N}]")
+    if not x.is_cuda:
+        logits = torch.empty(M, N, dtype=torch.float32)
+        ref.gemm(x, w, logits, layout_a=KMAJ, layout_b=KMAJ, M=M, N=N, K=K, bias=bias)
+        ref.softmax_xent(logits, labels, dz[:M, :N], n_cls, scale, loss_part, correct,
+                         XENT_ROWS_PER_BLOCK, colsum)
+        return dz
+    for name, t in (("x", x), ("w", w)):
+        if t.data_ptr() % 16 or t.stride(0) % 8:
+            raise ValueError(f"linear_xent_stream: rows of {name} must be 16-byte aligned")
+    assert native().xent_stream_max_k() == XENT_STREAM_MAX_K
+    native().xent_stream(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(labels), _p(dz),
+                         dz.stride(0), M, N, K, int(n_cls), float(scale), _p(loss_part),
+                         _p(correct), _p(colsum),
+                         colsum.stride(0) if colsum is not None else 0, _stream(x))
+    return dz
+
+
 DENSE_LOSS_CODE = {"mse": 1, "bce": 2}  # csrc/kernels/dense_loss.hpp DenseLoss
 DENSE_LOSS_ACTS = {"mse": ("linear", "relu", "sigmoid"), "bce": ("sigmoid",)}
 DENSE_COLS_PER_CHUNK = 256  # csrc/kernels/dense_loss.hip DL_COLS

@@ -29,6 +29,9 @@ SWITCHES: dict[str, tuple[str, str]] = {
                              "the producing GEMMs: auto (layers >= 16M weights) | 1 | 0"),
     "DNN_TAIL": ("1", "fused classifier tail kernel (mlp_tail.hip)"),
     "DNN_FUSED_XENT": ("1", "softmax cross-entropy fused into the logits GEMM epilogue"),
+    "DNN_XENT_STREAM": ("0", "1 = softmax classifiers wider than the GEMM-fused head train on "
+                             "the logits-free streaming kernel (xent_stream.hip: the last "
+                             "layer's input up to 1024 wide); 0 = fp32 logits + softmax_xent"),
     "DNN_RELU_MASK": ("auto", "1-bit ReLU masks instead of the activation in dgrad epilogues: "
                                  "1 = row-block-major bytes, 2 = fragment order (ops.FragMask, "
                                  "register-direct tiles only), 0 = off, auto = 2 for hidden "
