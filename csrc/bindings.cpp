@@ -30,6 +30,7 @@
 #include "kernels/mlp_tail.hpp"
 #include "kernels/mxfp4.hpp"
 #include "kernels/stage_fwd.hpp"
+#include "kernels/stage_gemv.hpp"
 #include "kernels/xent_stream.hpp"
 #include "runtime/blaslt.hpp"
 #include "runtime/chain_host.hpp"
@@ -71,6 +72,8 @@ static void check(int rc, const char* what) {
       msg += dnn::mlp_tail_error(rc);
     else if (std::string(what) == "stage_fwd")
       msg += dnn::stage_fwd_error(rc);
+    else if (std::string(what) == "stage_gemv")
+      msg += dnn::stage_gemv_error(rc);
     else if (std::string(what) == "blas_gemm") msg += dnn::blas_error(rc);
     else msg += "precondition/launch error code " + std::to_string(rc);
     if (rc == -9) msg += std::string(" (") + hipGetErrorString(hipGetLastError()) + ")";
@@ -504,6 +507,59 @@ PYBIND11_MODULE(_native, m) {
   m.def("stage_fwd_limits", []() {
     return std::make_tuple(dnn::STAGE_FWD_MAX_LAYERS, dnn::STAGE_FWD_MAX_WIDTH,
                            dnn::STAGE_FWD_TILES);
+  });
+  // Fused stage forward for 1..8 rows. layers: (w, ldw, bias, N, K, act) per layer. Every
+  // pointer -- the workspace and the counter too -- is routed through Program::fix.
+  m.def(
+      "stage_gemv",
+      [](uintptr_t x, long ldx, int rows, int K0,
+         const std::vector<std::tuple<uintptr_t, long, uintptr_t, int, int, int>>& layers,
+         uintptr_t y, long ldy, int out_f32, int n_cls, uintptr_t work, uintptr_t counter,
+         uintptr_t stream) {
+        if (layers.size() > (size_t)dnn::STAGE_GEMV_MAX_LAYERS)
+          check(-1, "stage_gemv");  // (more layers than StageGemvParams holds)
+        dnn::StageGemvParams p{};
+        p.x = P<const uint16_t>(x);
+        p.ldx = ldx;
+        p.rows = rows;
+        p.K0 = K0;
+        p.L = (int)layers.size();
+        for (int l = 0; l < p.L; ++l) {
+          dnn::StageGemvLayer& ly = p.layer[l];
+          ly.W = P<const uint16_t>(std::get<0>(layers[l]));
+          ly.ldw = std::get<1>(layers[l]);
+          ly.bias = P<const float>(std::get<2>(layers[l]));
+          ly.N = std::get<3>(layers[l]);
+          ly.K = std::get<4>(layers[l]);
+          ly.act = std::get<5>(layers[l]);
+        }
+        p.y = P<void>(y);
+        p.ldy = ldy;
+        p.out_f32 = out_f32;
+        p.n_cls = n_cls;
+        p.work = P<uint16_t>(work);
+        p.counter = P<uint32_t>(counter);
+        launch(
+            "stage_gemv",
+            [=](hipStream_t s, const dnn::Program& R) {
+              dnn::StageGemvParams q = p;
+              q.x = R.fix(q.x);
+              q.y = R.fix(q.y);
+              q.work = R.fix(q.work);
+              q.counter = R.fix(q.counter);
+              for (int l = 0; l < q.L; ++l) {
+                q.layer[l].W = R.fix(q.layer[l].W);
+                q.layer[l].bias = R.fix(q.layer[l].bias);
+              }
+              return dnn::stage_gemv(q, s);
+            },
+            stream);
+      },
+      py::arg("x"), py::arg("ldx"), py::arg("rows"), py::arg("K0"), py::arg("layers"),
+      py::arg("y"), py::arg("ldy"), py::arg("out_f32"), py::arg("n_cls"), py::arg("work"),
+      py::arg("counter"), py::arg("stream"));
+  m.def("stage_gemv_limits", []() {
+    return std::make_tuple(dnn::STAGE_GEMV_MAX_LAYERS, dnn::STAGE_GEMV_MAX_WIDTH);
   });
   // Grouped GEMM launch (no epilogue extras: the split-K weight gradients of a step). problems:
   // (a, lda, b, ldb, c, ldc, c_split_stride, M, N, K, k_total, accumulate, splits)

@@ -64,6 +64,13 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "the training GEMM (ops.linear_fwd); stream = the weight-streaming "
                          "GEMM (ops.linear_fwd_stream: weights straight into the MFMA "
                          "registers, K split inside the workgroup)")
+    ap.add_argument("--stage-gemv", choices=["layers", "fused"], default="layers",
+                    help="bf16 stages, requests of at most 8 rows: layers = one launch per "
+                         "layer; fused = all layers of a stage in one launch, the first "
+                         "layer on the whole chip, the others in the workgroup that "
+                         "finishes last (stages of 2..8 layers, padded widths after the "
+                         "input <= 512; anything else runs per layer). Bit for bit the "
+                         "per-layer answers")
     ap.add_argument("--stage-gemm", choices=["layers", "fused"], default="layers",
                     help="bf16 stages, buckets of more than 8 rows: layers = one launch per "
                          "layer; fused = all layers of a stage in one launch, the hidden "
@@ -304,7 +311,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             eng = InferenceEngine([mc.layers[p.layer_start:p.layer_end] for p in plans], dev,
                                   expected_input=input_dim, names=[s["name"] for s in stage_entries],
                                   weights=a.weights, fp8_gemm=a.fp8_gemm,
-                                  mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm,
+                                  mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm, stage_gemv=a.stage_gemv,
                                   bf16_gemm=a.bf16_gemm)
             server = serve(eng.predict, port=a.port, name=stage_entries[0]["name"])
         elif mode == "workers":
@@ -331,6 +338,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                 e["STAGE_FP8_GEMM"] = a.fp8_gemm
                 e["STAGE_MXFP4_GEMM"] = a.mxfp4_gemm
                 e["STAGE_GEMM"] = a.stage_gemm
+                e["STAGE_GEMV"] = a.stage_gemv
                 e["STAGE_BF16_GEMM"] = a.bf16_gemm
                 e["LOCAL_RANK"] = str(k)
                 stage_envs.append(e)
@@ -349,7 +357,8 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
                        "device": "cpu" if a.device == "cpu" else "auto",
                        "weights": a.weights, "fp8_gemm": a.fp8_gemm,
                        "mxfp4_gemm": a.mxfp4_gemm, "mxfp4_chain": a.mxfp4_chain,
-                       "stage_gemm": a.stage_gemm, "bf16_gemm": a.bf16_gemm},
+                       "stage_gemm": a.stage_gemm, "stage_gemv": a.stage_gemv,
+                       "bf16_gemm": a.bf16_gemm},
                       open(plan_path, "w"))
             job = spawn_ranks("docker_dist_nn_amd.serve.chain", ["--plan", plan_path], n_st,
                               devices=list(range(n_st)) if a.device != "cpu" else None,

@@ -52,6 +52,13 @@ def build_parser(script_dir: str) -> argparse.ArgumentParser:
                          "ops.BF16_STREAM_MAX_ROWS rows: tiled = the training GEMM (ops.linear_fwd); stream = the weight-streaming "
                          "GEMM (ops.linear_fwd_stream: weights straight into the MFMA "
                          "registers, K split inside the workgroup)")
+    ap.add_argument("--stage-gemv", choices=["layers", "fused"], default="layers",
+                    help="with --local, bf16 stages, requests of at most 8 rows: layers = one launch per "
+                         "layer; fused = all layers of a stage in one launch, the first "
+                         "layer on the whole chip, the others in the workgroup that "
+                         "finishes last (stages of 2..8 layers, padded widths after the "
+                         "input <= 512; anything else runs per layer). Bit for bit the "
+                         "per-layer answers")
     ap.add_argument("--stage-gemm", choices=["layers", "fused"], default="layers",
                     help="with --local, bf16 weights, buckets of more than 8 rows: layers = one launch per "
                          "layer; fused = all layers of a stage in one launch, the hidden "
@@ -103,7 +110,7 @@ def main(argv: Optional[list[str]] = None, script_dir: str = SCRIPT_DIR_DEFAULT)
             else torch.device("cuda", 0)
         eng = InferenceEngine([mc.layers], dev, expected_input=mc.layers[0].in_dim,
                               weights=a.weights, fp8_gemm=a.fp8_gemm,
-                              mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm,
+                              mxfp4_gemm=a.mxfp4_gemm, stage_gemm=a.stage_gemm, stage_gemv=a.stage_gemv,
                               bf16_gemm=a.bf16_gemm)
 
         def call(batch):

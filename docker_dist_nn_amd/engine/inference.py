@@ -38,6 +38,7 @@ WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
 FP8_GEMMS = ("scratch", "direct", "w8a8")
 MXFP4_GEMMS = ("scratch", "w4a8")
 STAGE_GEMMS = ("layers", "fused")
+STAGE_GEMVS = ("layers", "fused")
 BF16_GEMMS = ("tiled", "stream")
 
 
@@ -121,6 +122,20 @@ class InferenceStage:
     ``"layers"``, agree within fp32 summation error and one bf16 rounding of a hidden
     activation, not bit for bit.
 
+    ``stage_gemv="fused"`` (bf16 weights; ignored by fp8 and mxfp4 stages; independent of
+    ``stage_gemm``) serves every bucket of at most ``ops.GEMV_MAX_ROWS`` rows with ONE launch of
+    ``ops.stage_gemv`` instead of one ``ops.gemv`` per layer plus ``ops.softmax_rows``: the first
+    layer runs on the whole chip, the workgroup that finishes last walks the other layers with
+    the activations in LDS. It applies when ``ops.stage_gemv_supported`` holds (the rule of
+    ``stage_gemm``) and ``upto`` is not set; ``buffers(rows)`` then also holds the kernel's
+    workspace (``"gemv_work"``) and its zeroed counter (``"gemv_counter"``) and marks the bucket
+    ``"gemv_fused"``. The hidden ``h`` buffers stay (they are 8 rows, and ``upto`` callers use
+    them). A last-layer softmax over more than 64 classes runs the kernel with a linear last
+    layer into fp32 and then ``ops.softmax_rows``. Everything else -- larger buckets, one-layer
+    stages, a hidden softmax, a wider layer, ``upto`` -- runs as without the option, without a
+    warning. The kernel sums in ``ops.gemv``'s order and rounds where the per-layer path
+    rounds: answers are bit for bit those of ``"layers"`` (the default).
+
     ``bf16_gemm="stream"`` (bf16 weights; ignored by fp8 and mxfp4 stages) runs every layer of
     a bucket of 9 .. ``ops.BF16_STREAM_MAX_ROWS`` rows on ``ops.linear_fwd_stream``, the
     weight-streaming GEMM (weights straight into the MFMA operand registers, K split inside the
@@ -136,7 +151,8 @@ class InferenceStage:
                  expected_input: int, name: str = "layer", is_last: bool = True,
                  case_sensitive: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
-                 stage_gemm: str = "layers", bf16_gemm: str = "tiled"):
+                 stage_gemm: str = "layers", bf16_gemm: str = "tiled",
+                 stage_gemv: str = "layers"):
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"weights must be one of {WEIGHT_FORMATS}, got {weights!r}")
         if fp8_gemm not in FP8_GEMMS:
@@ -147,6 +163,9 @@ class InferenceStage:
             raise ValueError(f"stage_gemm must be one of {STAGE_GEMMS}, got {stage_gemm!r}")
         if bf16_gemm not in BF16_GEMMS:
             raise ValueError(f"bf16_gemm must be one of {BF16_GEMMS}, got {bf16_gemm!r}")
+        if stage_gemv not in STAGE_GEMVS:
+            raise ValueError(f"stage_gemv must be one of {STAGE_GEMVS}, got {stage_gemv!r}")
+        self.stage_gemv = stage_gemv
         self.stage_gemm = stage_gemm
         self.bf16_gemm = bf16_gemm
         self.weights = weights
@@ -191,6 +210,9 @@ class InferenceStage:
             self._fused_acts[-1] = "linear"
         self._fused_ok = (weights == "bf16" and stage_gemm == "fused" and
                           ops.stage_fwd_supported(self.pads, self._fused_acts, self.dims[-1]))
+        self._gemv_fused_ok = (weights == "bf16" and stage_gemv == "fused" and
+                               ops.stage_gemv_supported(self.pads, self._fused_acts,
+                                                        self.dims[-1]))
         # fp8 / mxfp4, buckets > 8 rows: one bf16 layer
         self._wscratch: Optional[torch.Tensor] = None
         self._bufs: dict[int, dict] = {}
@@ -262,6 +284,11 @@ class InferenceStage:
                     b["xq"].append(torch.zeros(rows, kp, dtype=torch.uint8, device=dev))
                     b["sx"].append(torch.zeros(rows, dtype=torch.float32, device=dev))
             b["fused"] = self._fused(rows)
+            b["gemv_fused"] = self._gemv_fused_ok and rows <= ops.GEMV_MAX_ROWS
+            if b["gemv_fused"]:  # ops.stage_gemv's hand-off between its workgroups
+                b["gemv_work"] = torch.zeros(ops.GEMV_MAX_ROWS * self.pads[1],
+                                             dtype=torch.bfloat16, device=dev)
+                b["gemv_counter"] = torch.zeros(1, dtype=torch.int32, device=dev)
             for i, np_ in enumerate(self.pads[1:]):
                 last = i == len(self.layers) - 1
                 need_f32 = (last and self.is_last) or self.acts[i] == "softmax"
@@ -282,10 +309,16 @@ class InferenceStage:
     def _forward_fused(self, b: dict, x: torch.Tensor) -> torch.Tensor:
         n_out = self.dims[-1]
         h, f = b["h"][-1], b["f32"][-1]
+        if b["gemv_fused"]:  # <= 8 rows: the GEMV form of the same stage, same arguments
+            def run(x, w, bias, acts, y, n_cls=0):
+                return ops.stage_gemv(x, w, bias, acts, y, b["gemv_work"], b["gemv_counter"],
+                                      n_cls=n_cls)
+        else:
+            run = ops.stage_fwd
         if self.acts[-1] != "softmax":
             out = f if self.is_last else h
-            return ops.stage_fwd(x, self.w, self.b, self._fused_acts, out)
-        ops.stage_fwd(x, self.w, self.b, self._fused_acts, f, n_cls=n_out)
+            return run(x, self.w, self.b, self._fused_acts, out)
+        run(x, self.w, self.b, self._fused_acts, f, n_cls=n_out)
         if self._fused_acts[-1] != "softmax":
             ops.softmax_rows(f, f, n_out)
         if self.is_last:
@@ -352,7 +385,7 @@ class InferenceStage:
         b = self.buffers(rows)
         if x is None:
             x = b["x"]
-        if upto is None and b["fused"]:
+        if upto is None and (b["fused"] or b["gemv_fused"]):
             return self._forward_fused(b, x)
         n = len(self.layers)
         for i in range(n if upto is None else upto):
@@ -382,10 +415,12 @@ class InferenceEngine:
                  expected_input: int, names: Optional[Sequence[str]] = None,
                  max_rows: int = 65536, use_graphs: bool = True, weights: str = "bf16",
                  fp8_gemm: str = "scratch", mxfp4_gemm: str = "scratch",
-                 stage_gemm: str = "layers", bf16_gemm: str = "tiled"):
+                 stage_gemm: str = "layers", bf16_gemm: str = "tiled",
+                 stage_gemv: str = "layers"):
         """``weights``: "bf16", "fp8" or "mxfp4", ``fp8_gemm``: "scratch", "direct" or "w8a8",
         ``mxfp4_gemm``: "scratch" or "w4a8", ``stage_gemm``: "layers" or "fused", ``bf16_gemm``:
-        "tiled" or "stream" (see :class:`InferenceStage`), for every stage."""
+        "tiled" or "stream", ``stage_gemv``: "layers" or "fused" (see :class:`InferenceStage`),
+        for every stage."""
         self.device = device
         self.stages: list[InferenceStage] = []
         exp = expected_input
@@ -394,7 +429,8 @@ class InferenceEngine:
             st = InferenceStage(ls, device, expected_input=exp, name=names[i],
                                 is_last=i == len(stage_layers) - 1, weights=weights,
                                 fp8_gemm=fp8_gemm, mxfp4_gemm=mxfp4_gemm,
-                                stage_gemm=stage_gemm, bf16_gemm=bf16_gemm)
+                                stage_gemm=stage_gemm, bf16_gemm=bf16_gemm,
+                                stage_gemv=stage_gemv)
             self.stages.append(st)
             exp = st.out_dim
         self.max_rows = max_rows

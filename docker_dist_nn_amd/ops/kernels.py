@@ -816,6 +816,75 @@ def stage_fwd(x, ws, biases, acts, y, n_cls=0, tile=0):
     return y
 
 
+def stage_gemv_supported(pads, acts, n_cls=0) -> bool:
+    """Whether the fused small-batch stage forward (:func:`stage_gemv`) serves a stage: the rule
+    of :func:`stage_fwd_supported` (2..8 layers, every padded width after the input a multiple
+    of 64 and at most 512, linear / relu / sigmoid layers, softmax on the last layer only and
+    over at most 64 classes)."""
+    return stage_fwd_supported(pads, acts, n_cls)
+
+
+def stage_gemv(x, ws, biases, acts, y, work, counter, n_cls=0):
+    """All layers of a stage for 1..GEMV_MAX_ROWS rows in ONE launch
+    (csrc/kernels/stage_gemv.hip): h_0 = x, h_{l+1} = bf16(act_l(h_l . ws[l]^T + biases[l])),
+    the last layer into ``y`` (bf16 or fp32), every sum in :func:`gemv`'s order: bit for bit
+    the chain of ``gemv`` launches (+ ``softmax_rows``) on the same operands. x bf16 [M][K0]
+    with 16-byte aligned rows (K0 % 8 == 0), ws[l] bf16 [N_l][N_{l-1}] padded weights read in
+    place, biases[l] fp32 [>= N_l] or None, y [>= M][>= N_last]; only rows < M and columns <
+    N_last of y are written. A softmax last layer (fp32 y) writes the probabilities over the
+    first ``n_cls`` columns and nothing beyond them. ``work``: bf16, >= 8 * N_0 elements, the
+    first layer's output on its way between workgroups; ``counter``: one int32, zero before the
+    first launch and left zero by every launch. Both belong to one launch at a time (one
+    stream). What the kernel serves: :func:`stage_gemv_supported`. CPU tensors run the
+    per-layer chain (reference.stage_fwd) and leave ``work`` and ``counter`` alone."""
+    acts = [_act(a) for a in acts]
+    L = len(ws)
+    if len(biases) != L or len(acts) != L:
+        raise ValueError("stage_gemv: one weight, bias and activation per layer")
+    _rows(x, "x", torch.bfloat16)
+    M, K = x.shape
+    if not 1 <= M <= GEMV_MAX_ROWS:
+        raise ValueError(f"stage_gemv takes 1..{GEMV_MAX_ROWS} rows, got {M}")
+    pads = [K]
+    for l, (w, b) in enumerate(zip(ws, biases)):
+        _rows(w, f"ws[{l}]", torch.bfloat16)
+        if w.shape[1] != pads[-1]:
+            raise ValueError(f"stage_gemv: layer {l} takes {w.shape[1]} inputs, the layer "
+                             f"before gives {pads[-1]}")
+        if b is not None and (b.dtype != torch.float32 or b.numel() < w.shape[0] or
+                              not b.is_contiguous()):
+            raise ValueError("bias must be contiguous fp32 with >= N entries")
+        pads.append(w.shape[0])
+    # (the input width is bound by % 8 only: the rule is asked with it rounded up)
+    if K % 8 or not stage_gemv_supported([-(-K // 64) * 64] + pads[1:], acts, n_cls):
+        raise ValueError(f"stage_gemv does not serve widths {pads} with activation codes "
+                         f"{acts} (n_cls {n_cls}): see stage_gemv_supported")
+    if y.dim() != 2 or y.shape[0] < M or y.shape[1] < pads[-1] or y.stride(1) != 1:
+        raise ValueError("stage_gemv operand shapes do not match")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("y must be bf16 or fp32")
+    if acts[-1] == 3 and y.dtype != torch.float32:
+        raise TypeError("a softmax last layer writes fp32 probabilities")
+    if work is None or work.dtype != torch.bfloat16 or not work.is_contiguous() or \
+            work.numel() < GEMV_MAX_ROWS * pads[1]:
+        raise ValueError(f"stage_gemv: work must be contiguous bf16 with >= "
+                         f"{GEMV_MAX_ROWS * pads[1]} elements")
+    if counter is None or counter.dtype != torch.int32 or counter.numel() < 1:
+        raise ValueError("stage_gemv: counter must be an int32 tensor")
+    if not x.is_cuda:
+        return ref.stage_fwd(x, ws, biases, acts, y, n_cls)
+    assert native().stage_gemv_limits() == (STAGE_FWD_MAX_LAYERS, STAGE_FWD_MAX_WIDTH)
+    for name, t in (("x", x), *((f"ws[{l}]", w) for l, w in enumerate(ws))):
+        if t.data_ptr() % 16 or t.stride(0) % 8:
+            raise ValueError(f"stage_gemv: rows of {name} must be 16-byte aligned")
+    native().stage_gemv(_p(x), x.stride(0), M, K,
+                        [(_p(w), w.stride(0), _p(b), w.shape[0], w.shape[1], a)
+                         for w, b, a in zip(ws, biases, acts)],
+                        _p(y), y.stride(0), int(y.dtype == torch.float32), int(n_cls),
+                        _p(work), _p(counter), _stream(x))
+    return y
+
+
 def linear_dgrad(dz, w, dx, y_prev=None, act_prev="linear", colsum=None, mask_prev=None,
                  wt=None, dxt=None):
     """dx[M][Kp] = (dz[M][Np] . w[Np][Kp]) * act_prev'(y_prev) (mask fused in the epilogue).

@@ -492,6 +492,7 @@ def main(argv: Optional[list[str]] = None) -> int:
                            fp8_gemm=plan.get("fp8_gemm", "scratch"),
                            mxfp4_gemm=plan.get("mxfp4_gemm", "scratch"),
                            stage_gemm=plan.get("stage_gemm", "layers"),
+                           stage_gemv=plan.get("stage_gemv", "layers"),
                            bf16_gemm=plan.get("bf16_gemm", "tiled"))
     cr = ChainRank(stage, rank, world, names, device,
                    hop_timeout=plan.get("hop_timeout", HOP_TIMEOUT_S))

@@ -17,7 +17,8 @@ quantises each layer's activations to e4m3; ignored by an mxfp4 stage), and STAG
 "scratch" (default) or "w4a8", how an mxfp4 stage runs those buckets (--mxfp4-gemm; "w4a8" runs
 the 4-bit codes against e4m3 activations; ignored by bf16 and fp8 stages), and STAGE_GEMM,
 "layers" (default) or "fused", whether a bf16 stage runs those buckets one launch per layer or
-all its layers in one (--stage-gemm), and STAGE_BF16_GEMM, "tiled" (default) or "stream", whether a
+all its layers in one (--stage-gemm), and STAGE_GEMV, "layers" (default) or "fused", the same
+choice for requests of at most 8 rows (--stage-gemv), and STAGE_BF16_GEMM, "tiled" (default) or "stream", whether a
 bf16 stage runs its buckets of 9 .. ops.BF16_STREAM_MAX_ROWS rows on the training GEMM or on the
 weight-streaming GEMM (--bf16-gemm; ignored by fp8 and mxfp4 stages). The values are passed to the
 engine unchanged.
@@ -88,6 +89,7 @@ class StageWorker:
                                fp8_gemm=env.get("STAGE_FP8_GEMM", "scratch") or "scratch",
                                mxfp4_gemm=env.get("STAGE_MXFP4_GEMM", "scratch") or "scratch",
                                stage_gemm=env.get("STAGE_GEMM", "layers") or "layers",
+                               stage_gemv=env.get("STAGE_GEMV", "layers") or "layers",
                                bf16_gemm=env.get("STAGE_BF16_GEMM", "tiled") or "tiled")
 
     def _client(self):
